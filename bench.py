@@ -10,6 +10,11 @@ including the reference's per-step pred_x0 / noise_pred log copies).  value = de
     python bench.py [--gpus N --steps K --warmup W]       (N > 1: bench.py starts its own N ranks)
     torchrun --nproc-per-node N bench.py --gpus N ...      (weak scaling: 8 latents per GPU)
 
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes runs of its
+own: the per-kernel timings and the dominant kernel's roofline, the CPU baseline and the config-1 / config-3 CPU
+legs (--no-kernel-timing / --no-cpu-baseline / --no-cpu-legs drop one of them again).  --dump-outputs DIR writes
+what the last timed step computed as DIR/<name>.npy (float32 / float64; see dump_outputs).
+
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py is its own launcher: before any GPU call it
 checks that N HIP devices are visible, starts N fresh worker processes of itself (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, the same env:// rendezvous and init_process_group("nccl")
@@ -58,14 +63,21 @@ def parse():
     ap.add_argument("--split", type=int, default=1,
                     help="run the per-GPU batch as this many sub-batch chains on separate streams (one graph)")
     ap.add_argument("--train-eager", action="store_true", help="train workload: no hipGraph capture of the step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cpu-legs", action="store_true", help="skip the config-1 / config-3 CPU legs")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-kernel timings + roofline of the "
+                         "dominant kernel, the CPU baseline, the config-1 / config-3 CPU legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cpu-legs", action="store_true", help="with --full: skip the config-1 / config-3 CPU legs")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel timings")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "r06", "pmc_traffic_step.json"),
                     help="per-kernel HBM traffic summary produced from a rocprofv3 --pmc pass (fp32 step kernels)")
     ap.add_argument("--pmc-lowp", default=os.path.join(ROOT, "profiles", "r06", "pmc_traffic_step_fp16.json"),
                     help="the same for the fp16 step kernels (config 5, DTYPE=fp16 tools/pmc_step_traffic.sh)")
     a = ap.parse_args()
+    if not a.full:          # a plain run: the timed steps and their result line only
+        a.no_cpu_baseline = a.no_cpu_legs = a.no_kernel_timing = True
     if a.batch is None:
         a.batch = {"train": 32, "stress": 1}.get(a.workload, 8)
     if a.timesteps is None:
@@ -75,6 +87,28 @@ def parse():
     if a.dtype is None:
         a.dtype = {"transfer": "fp16", "train": "bf16"}.get(a.workload, "fp32")
     return a
+
+
+DUMP_MAX_ELEMS = 4 << 20     # per array: 16 MB of float32 (at most three arrays per workload, < 64 MB in all)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each array of `arrays` (name -> tensor / sequence of numbers) as out_dir/<name>.npy,
+    float64 kept, everything else as float32.  An array above DUMP_MAX_ELEMS elements is written as a fixed sample
+    of them: the flat elements at DUMP_MAX_ELEMS sorted indices drawn by numpy's default_rng(0), the same for every
+    run and build, so two runs' files compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().to("cpu")
+            a = (a if a.dtype == torch.float64 else a.float()).contiguous().numpy()
+        else:
+            a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_ELEMS))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def layer_flops(d):
@@ -396,6 +430,9 @@ def run_train(args, world, rank, dev, M):
         elapsed = float(tt.item())
     if not all(map(lambda v: v == v and abs(v) != float("inf"), losses.values())):
         raise SystemExit(f"non-finite losses {losses}")
+    if args.dump_outputs and rank == 0:
+        # what train_step hands its caller: the last step's losses, one file each
+        dump_outputs(args.dump_outputs, {"loss_" + k: [v] for k, v in losses.items()})
     ms_step = elapsed / args.steps * 1e3
     value = B * world * args.steps / elapsed
     flops = TRAIN_GFLOP_PER_SAMPLE * 1e9 * B
@@ -498,6 +535,8 @@ def run_stress(args, world, rank, dev, M):
         elapsed = time.perf_counter() - t0
     if not torch.isfinite(x).all():
         raise SystemExit("non-finite sample")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sample": x, "pred_x0_logs": x0_logs, "noise_pred_logs": eps_logs})
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -713,6 +752,9 @@ def main():
         elapsed = time.perf_counter() - t0
     if not torch.isfinite(gd.x).all():
         raise SystemExit("non-finite sample")
+    if args.dump_outputs and rank == 0:
+        # what the reverse loop hands its caller: the sample and the per-iteration pred_x0 / noise_pred logs
+        dump_outputs(args.dump_outputs, {"sample": gd.x, "pred_x0_logs": gd.x0_logs, "noise_pred_logs": gd.eps_logs})
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)

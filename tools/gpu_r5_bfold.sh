@@ -12,5 +12,5 @@ for r in 1 2; do
     echo "round $r fold=$f: $(grep pairs $O/loop_${r}_$f.txt)"
   done
 done
-timeout -k 10 300 python -u bench.py --no-cpu-legs --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --no-cpu-legs --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 cat $O/bench.json

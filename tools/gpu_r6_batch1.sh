@@ -50,7 +50,7 @@ for sp in 1 2; do
       > $OUT/transfer_$sp.json 2> $OUT/transfer.err || { tail -20 $OUT/transfer.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/transfer_$sp.json')); print('transfer split $sp', d['us_per_denoise_iteration'], 'us/iter')"
 done
-timeout -k 10 240 python -u bench.py --workload stress --steps 3 --warmup 1 > $OUT/stress.json 2> $OUT/stress.err \
+timeout -k 10 240 python -u bench.py --full --workload stress --steps 3 --warmup 1 > $OUT/stress.json 2> $OUT/stress.err \
     || { tail -20 $OUT/stress.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/stress.json')); print('stress', d['us_per_denoise_iteration'], 'us/iter', d.get('roofline'), d.get('cpu_baseline', {}).get('value'))"
 cd /tmp && export TMPDIR=/tmp

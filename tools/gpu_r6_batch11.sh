@@ -12,7 +12,7 @@ rc=$?; tail -2 $OUT/tests.log
 if [ $rc -ne 0 ]; then grep -E "^FAILED|^ERROR|Error" $OUT/tests.log | head; echo "tests exited $rc: stopping"; exit $rc; fi
 for r in 1 2; do
   for m in 0 1; do
-    LDM_CIN1_S1=$m timeout -k 10 240 python -u bench.py --workload stress --steps 3 --warmup 1 --no-cpu-baseline \
+    LDM_CIN1_S1=$m timeout -k 10 240 python -u bench.py --full --workload stress --steps 3 --warmup 1 --no-cpu-baseline \
         > $OUT/stress_${r}_$m.json 2> $OUT/stress.err || { tail -20 $OUT/stress.err; exit 1; }
     python -c "import json; d=json.load(open('$OUT/stress_${r}_$m.json')); print('round $r cin1_s1=$m', d['us_per_denoise_iteration'], 'us/iter')"
   done

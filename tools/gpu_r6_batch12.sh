@@ -12,7 +12,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_store16.py tests/test_gpu_s
 rc=$?; tail -2 $OUT/tests.log
 if [ $rc -ne 0 ]; then grep -E "^FAILED|^ERROR|Error" $OUT/tests.log | head; echo "tests exited $rc: stopping"; exit $rc; fi
 stress() {
-  timeout -k 10 240 python -u bench.py --workload stress --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stress_$1.json 2> $OUT/stress.err \
+  timeout -k 10 240 python -u bench.py --full --workload stress --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stress_$1.json 2> $OUT/stress.err \
       || { tail -20 $OUT/stress.err; return 1; }
   python -c "import json; d=json.load(open('$OUT/stress_$1.json')); print('$1', d['us_per_denoise_iteration'], 'us/iter')"
 }

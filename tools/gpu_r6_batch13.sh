@@ -12,7 +12,7 @@ rc=$?; tail -2 $OUT/tests.log
 if [ $rc -ne 0 ]; then grep -E "^FAILED|^ERROR|Error|assert" $OUT/tests.log | head -20; echo "tests exited $rc: stopping"; exit $rc; fi
 for r in 1 2; do
   for m in 0 1; do
-    LDM_FLASH_SPLIT=$m timeout -k 10 240 python -u bench.py --workload stress --steps 3 --warmup 1 --no-cpu-baseline \
+    LDM_FLASH_SPLIT=$m timeout -k 10 240 python -u bench.py --full --workload stress --steps 3 --warmup 1 --no-cpu-baseline \
         > $OUT/stress_${r}_$m.json 2> $OUT/stress.err || { tail -20 $OUT/stress.err; exit 1; }
     python -c "import json; d=json.load(open('$OUT/stress_${r}_$m.json')); print('round $r flash_split=$m', d['us_per_denoise_iteration'], 'us/iter', d['roofline']['avg_launch_us'])"
   done

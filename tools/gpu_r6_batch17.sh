@@ -10,7 +10,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_attention_wide.py tests/tes
     --timeout 300 --timeout-method thread > $OUT/tests.log 2>&1
 rc=$?; tail -2 $OUT/tests.log
 if [ $rc -ne 0 ]; then grep -E "^FAILED|^ERROR|Error|assert" $OUT/tests.log | head -20; echo "tests exited $rc: stopping"; exit $rc; fi
-timeout -k 10 240 python -u bench.py --workload stress --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stress.json 2> $OUT/stress.err \
+timeout -k 10 240 python -u bench.py --full --workload stress --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stress.json 2> $OUT/stress.err \
     || { tail -20 $OUT/stress.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/stress.json')); print('stress', d['us_per_denoise_iteration'], 'us/iter')"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof_stress -o run -- \

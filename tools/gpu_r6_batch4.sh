@@ -20,7 +20,7 @@ for r in 1 2; do
   trn u2_$r LDM_BN_UNROLL=2 || exit 1
   trn u4_$r LDM_BN_UNROLL=4 || exit 1
 done
-timeout -k 10 300 python -u bench.py --workload stress --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stress.json 2> $OUT/stress.err \
+timeout -k 10 300 python -u bench.py --full --workload stress --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stress.json 2> $OUT/stress.err \
     || { tail -20 $OUT/stress.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/stress.json')); print('stress', d['us_per_denoise_iteration'], 'us/iter', d.get('roofline'))"
 cd /tmp && export TMPDIR=/tmp

@@ -31,7 +31,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_attention_wide.py tests/tes
     --timeout 240 --timeout-method thread > $OUT/tests_kh.log 2>&1 || { tail -30 $OUT/tests_kh.log; exit 1; }
 tail -1 $OUT/tests_kh.log
 for kh in 1 0; do
-  LDM_FLASH_KH=$kh timeout -k 10 300 python -u bench.py --workload stress --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stress_kh$kh.json 2> $OUT/stress.err \
+  LDM_FLASH_KH=$kh timeout -k 10 300 python -u bench.py --full --workload stress --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stress_kh$kh.json 2> $OUT/stress.err \
       || { tail -20 $OUT/stress.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/stress_kh$kh.json')); print('stress kh=$kh', d['us_per_denoise_iteration'], 'us/iter', d['roofline']['avg_launch_us'], d['roofline']['frac'])"
 done

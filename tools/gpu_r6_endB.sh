@@ -7,7 +7,7 @@ T=${1:-r6end}; O=$PWD/gpurun_out/$T; mkdir -p $O
 export PYTHONUNBUFFERED=1
 bash tools/gpu_final.sh $T/final || exit 1
 bash tools/gpu_workloads.sh $T/workloads || exit 1
-timeout -k 10 300 python -u bench.py --workload stress --steps 3 --warmup 1 > $O/stress.json 2> $O/stress.err \
+timeout -k 10 300 python -u bench.py --full --workload stress --steps 3 --warmup 1 > $O/stress.json 2> $O/stress.err \
     || { echo "stress failed"; tail -20 $O/stress.err; exit 1; }
 cat $O/stress.json
 cd /tmp && export TMPDIR=/tmp

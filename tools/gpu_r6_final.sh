@@ -26,7 +26,7 @@ cp $OUT/pmc_train/summary.json profiles/r06/train_pmc.json
 python3 -c "import json; d=json.load(open('profiles/r06/train_pmc.json')); print('train HBM bytes/step', d.get('step_hbm_bytes'), 'mfma util', d.get('step_mfma_util'))"
 bash tools/gpu_final.sh $T/final || exit 1
 bash tools/gpu_workloads.sh $T/workloads || exit 1
-timeout -k 10 300 python -u bench.py --workload stress --steps 3 --warmup 1 > $OUT/stress.json 2> $OUT/stress.err \
+timeout -k 10 300 python -u bench.py --full --workload stress --steps 3 --warmup 1 > $OUT/stress.json 2> $OUT/stress.err \
     || { echo "stress failed"; tail -20 $OUT/stress.err; exit 1; }
 cat $OUT/stress.json
 cd /tmp && export TMPDIR=/tmp

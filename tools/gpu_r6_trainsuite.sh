@@ -13,7 +13,7 @@ tail -2 $OUT/tests.log
 timeout -k 10 240 python -u bench.py --workload train --steps 20 --warmup 3 --no-cpu-baseline > $OUT/train.json 2> $OUT/train.err \
     || { tail -20 $OUT/train.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/train.json')); print('train', round(d['ms_per_step'],4), 'ms')"
-timeout -k 10 240 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/sample.json 2> $OUT/sample.err \
+timeout -k 10 240 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/sample.json 2> $OUT/sample.err \
     || { tail -20 $OUT/sample.err; exit 1; }
 python -c "
 import json; d=json.load(open('$OUT/sample.json')); print('sample', d['value'], d['us_per_denoise_iteration'] if 'us_per_denoise_iteration' in d else '')

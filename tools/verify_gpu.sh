@@ -7,5 +7,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-me
 rc=$?
 tail -4 $O/gpu_tests.log
 if [ $rc -ne 0 ]; then echo "FAILED: pytest -m gpu exited $rc (bench not run)"; exit $rc; fi
-timeout -k 10 300 python -u bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
