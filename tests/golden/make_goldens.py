@@ -7,6 +7,7 @@
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_goldens.py --vggish # ref_goldens_vggish.npz
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_goldens.py --r3     # ref_goldens_r3.npz
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_goldens.py --fp16train   # ref_goldens_fp16.npz
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_goldens.py --shapeS # ref_goldens_shapeS.npz
 
 Imports /root/reference/models/model.py and loss.py with two absent, unused-on-this-path imports
 stubbed (``pytorch_lightning`` at model.py:4 and ``lpips`` at loss.py:3) and with
@@ -600,6 +601,31 @@ def fp16train():
     print("wrote", path, os.path.getsize(path), "bytes,", len(G), "arrays")
 
 
+def shape_s():
+    """(14) SURVEY shape S at its FULL size -> tests/golden/ref_goldens_shapeS.npz: the reference UNet(1, 1, 64),
+    eval(), recipe weights (seed 105), straight on a raw [1,1,128,512] mel with style maps s5 [1,256,32,128] and
+    s6 [1,512,16,64] (CA2 L = S = 4096, CA1 1024), t = 117 -- the weights and inputs of tests/test_gpu_shape_s.py
+    (_unet, _inputs(1, .)), the forward bench.py --workload stress times.  Stored: t, the output, the time
+    embedding."""
+    torch.set_num_threads(8)
+    M, _ = import_reference()
+    G = {}
+    with torch.no_grad():
+        u = M.UNet(1, 1, 64)
+        recipe.fill_module(u, seed=105)
+        u.eval()
+        z = torch.from_numpy(recipe.normal((1, 1, 128, 512), 780))
+        s5 = torch.from_numpy(recipe.uniform01((1, 256, 32, 128), 781))
+        s6 = torch.from_numpy(recipe.uniform01((1, 512, 16, 64), 782))
+        t = torch.tensor([117], dtype=torch.long)
+        G["shapeS_full_t"] = t.numpy()
+        G["shapeS_full_out"] = np32(u(z, t, {"s5": s5, "s6": s6}))
+        G["shapeS_full_temb"] = np32(u.time_mlp(t))
+    path = os.path.join(HERE, "ref_goldens_shapeS.npz")
+    np.savez_compressed(path, **G)
+    print("wrote", path, os.path.getsize(path), "bytes,", len(G), "arrays")
+
+
 TRAIN_GRAD_KEYS = ("unet.time_mlp.1.weight", "unet.dec1.weight", "unet.dec1.bias", "unet.enc1.weight",
                    "unet.cross_attention1.multihead_attn.in_proj_weight", "unet.bottleneck.bias",
                    "decoder.decoder.6.weight", "decoder.decoder.1.weight", "style_encoder.enc6.bias",
@@ -613,6 +639,8 @@ AE_KEYS = ("encoder.encoder.0.weight", "encoder.encoder.1.weight", "encoder.enco
 if __name__ == "__main__":
     if "--fp16train" in sys.argv:
         fp16train()
+    elif "--shapeS" in sys.argv:
+        shape_s()
     elif "--r2" in sys.argv:
         round2()
     elif "--r3" in sys.argv:

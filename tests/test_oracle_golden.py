@@ -295,3 +295,22 @@ def test_config3_train_step(M, goldens3):
     assert rel_err(o["reconstructed"].detach()[[0, B - 1]].numpy(), goldens3["r3_fp32_recon_0_31"]) < 1e-5
     for k in ("unet.dec1.weight", "decoder.decoder.6.weight"):
         assert rel_err(sd[k].grad.numpy(), goldens3["r3_fp32_grad_" + k]) < 1e-4, k
+
+
+# ---- shape S at its full size (ref_goldens_shapeS.npz) ----------------------------------------------------
+def test_shape_s_full_size_unet(M):
+    """UNet(1, 1, 64) on the raw [1,1,128,512] mel with s5 [1,256,32,128], s6 [1,512,16,64] (CA2 L = S = 4096,
+    CA1 1024): the weights and inputs of tests/test_gpu_shape_s.py, against the reference's own forward
+    (make_goldens.py --shapeS).  fp32 CPU both: 2e-6 (measured 2.7e-7)."""
+    import os
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_goldens_shapeS.npz"))
+    sd = sd_for(lambda: M.UNet(1, 1, 64), 105)
+    z = torch.from_numpy(recipe.normal((1, 1, 128, 512), 780))
+    s5 = torch.from_numpy(recipe.uniform01((1, 256, 32, 128), 781))
+    s6 = torch.from_numpy(recipe.uniform01((1, 512, 16, 64), 782))
+    t = torch.from_numpy(g["shapeS_full_t"])
+    assert t.tolist() == [117]
+    with torch.no_grad():
+        y = TC.unet(sd, z, t, s5, s6, p="")
+    assert rel_err(y.numpy(), g["shapeS_full_out"]) < 2e-6
+    assert rel_err(NP.time_mlp(sd, "", g["shapeS_full_t"]), g["shapeS_full_temb"]) < 2e-5
