@@ -371,6 +371,46 @@ int ldm_mel_quantize(const float* db, uint8_t* out, int64_t n, float max_db, voi
 int ldm_mel_dequantize(const uint8_t* in, float* db, int64_t n, float max_db, void* stream);
 int ldm_u8_to_unit(const uint8_t* in, float* out, int64_t n, void* stream);
 
+/* ---- audio front and back end (audio.hip; DESIGN.md "Audio front and back end") ------------------------
+ * librosa's defaults: periodic Hann window of n_fft points, hop = n_fft / 4, centre reflect padding.  Built for
+ * n_fft 512 and 2048; everything fp32.  Complex arrays are interleaved (re, im) pairs; spectra are [B, F, T] with
+ * F = n_fft/2 + 1 and T = 1 + L / hop frames (T contiguous).
+ *
+ * tables: the twiddle / window table of one n_fft on the device: ldm_stft_table_floats(n_fft) floats (0 for an
+ * unsupported n_fft), filled on the host in float64 by ldm_stft_fill_tables and copied over by the caller.
+ * ldm_stft: y [B, L] (L >= n_fft/2 + 1) -> S complex and / or mag = |S|^power (power 1 or 2); either may be null.
+ * ldm_istft: y [B, L] = overlap-add of the inverse frames of S (times mag [B, F, T] elementwise when mag is not
+ * null), divided by the window sum-of-squares envelope where it exceeds the smallest normal fp32, the n_fft/2
+ * centre padding trimmed; 1 <= L <= (T + 1) * hop.  Gather form, fixed order: bitwise repeatable.
+ * ldm_griffinlim: n_iter iterations of  y = istft(mag * angles); r = stft(y); angles = unit(r - m/(1+m) r_prev);
+ * r_prev = r  from angles = init_angles [B, F, T] complex, then y [B, L] = istft(mag * angles); L must give T
+ * frames.  Two launches per iteration on `stream`, no host synchronisation or allocation (capturable); workspace:
+ * ldm_griffinlim_workspace(B, n_fft, T) floats.
+ * ldm_mel_project: mel [B, n_mels, T] = M . P [B, F, T]; M [n_mels, F] dense, lohi [n_mels][2] each row's
+ * non-zero run [lo, hi).
+ * ldm_power_to_db: per item b of x [B, n]: 10 log10(max(x, amin)) - 10 log10(max(amin, max_b x)), clamped below at
+ * -top_db when top_db >= 0; workspace: B floats.  ldm_db_to_power: 10^(x / 10).
+ * ldm_mel_invert: x [B, F, T] = max(Minv . mel, 0), then `iters` steps  x = max(x - Mt (M x - mel) * inv_lambda, 0),
+ * then sqrt when take_sqrt; Mt [F, n_mels] = M transposed, Minv [F, n_mels]; workspace: B * n_mels * T floats. */
+int64_t ldm_stft_table_floats(int32_t n_fft);
+int ldm_stft_fill_tables(int32_t n_fft, float* host_tables);
+int ldm_stft(const float* y, int32_t B, int64_t L, int32_t n_fft, int32_t hop, const float* tables, float* S,
+             float* mag, int32_t power, void* stream);
+int ldm_istft(const float* S, const float* mag, float* y, int32_t B, int32_t T, int64_t L, int32_t n_fft,
+              int32_t hop, const float* tables, void* stream);
+int64_t ldm_griffinlim_workspace(int32_t B, int32_t n_fft, int32_t T);
+int ldm_griffinlim(const float* mag, const float* init_angles, float* y, int32_t B, int32_t T, int64_t L,
+                   int32_t n_fft, int32_t hop, int32_t n_iter, float momentum, const float* tables,
+                   float* workspace, void* stream);
+int ldm_mel_project(const float* P, const float* M, const int32_t* lohi, float* mel, int32_t B, int32_t F,
+                    int32_t n_mels, int32_t T, void* stream);
+int ldm_power_to_db(const float* x, float* out, int32_t B, int64_t n, float amin, float top_db, float* workspace,
+                    void* stream);
+int ldm_db_to_power(const float* x, float* out, int64_t n, void* stream);
+int ldm_mel_invert(const float* mel, const float* M, const float* Mt, const float* Minv, const int32_t* lohi,
+                   float inv_lambda, int32_t iters, int32_t take_sqrt, float* x, float* workspace, int32_t B,
+                   int32_t F, int32_t n_mels, int32_t T, void* stream);
+
 /* ---- step kernels (uconv.hip): fixed-structure implicit GEMMs of the nine UNet convs -------------------
  * Packed size (floats) of layer `layer` (0..8 = enc1..dec1) and its packing from the torch weight layout
  * (conv [Cout][Cin][3][3], transposed conv [Cin][Cout][3][3]).  ldm_step_conv runs one layer on NHWC

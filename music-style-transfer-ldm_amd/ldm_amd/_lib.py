@@ -106,6 +106,19 @@ SIGNATURES = {
     "ldm_mel_quantize": (c_int32, [c_fp, c_fp, c_int64, ctypes.c_float, c_vp]),
     "ldm_mel_dequantize": (c_int32, [c_fp, c_fp, c_int64, ctypes.c_float, c_vp]),
     "ldm_u8_to_unit": (c_int32, [c_fp, c_fp, c_int64, c_vp]),
+    # audio front and back end (audio.hip)
+    "ldm_stft_table_floats": (c_int64, [c_int32]),
+    "ldm_stft_fill_tables": (c_int32, [c_int32, c_vp]),
+    "ldm_stft": (c_int32, [c_fp, c_int32, c_int64, c_int32, c_int32, c_fp, c_fp, c_fp, c_int32, c_vp]),
+    "ldm_istft": (c_int32, [c_fp, c_fp, c_fp, c_int32, c_int32, c_int64, c_int32, c_int32, c_fp, c_vp]),
+    "ldm_griffinlim_workspace": (c_int64, [c_int32, c_int32, c_int32]),
+    "ldm_griffinlim": (c_int32, [c_fp, c_fp, c_fp, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_float,
+                                 c_fp, c_fp, c_vp]),
+    "ldm_mel_project": (c_int32, [c_fp, c_fp, c_vp, c_fp, c_int32, c_int32, c_int32, c_int32, c_vp]),
+    "ldm_power_to_db": (c_int32, [c_fp, c_fp, c_int32, c_int64, c_float, c_float, c_fp, c_vp]),
+    "ldm_db_to_power": (c_int32, [c_fp, c_fp, c_int64, c_vp]),
+    "ldm_mel_invert": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_vp, c_float, c_int32, c_int32, c_fp, c_fp, c_int32,
+                                 c_int32, c_int32, c_int32, c_vp]),
     "ldm_batchnorm_train": (c_int32, [c_fp, c_int32, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_float, c_float,
                                       c_int32, c_fp, c_fp, c_fp, c_vp]),
     "ldm_batchnorm_train_out": (c_int32, [c_fp, c_fp, c_int32, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_float,

@@ -1036,3 +1036,119 @@ def std_mse_accumulate(p, t, acc, scale, eps=1e-8, out=None):
     L.call("ldm_std_mse_accumulate", mom.data_ptr(), B, n, float(eps), float(scale), acc.data_ptr(), _p(out),
            stream_handle())
     return mom
+
+
+# ---- audio front and back end (audio.hip; DESIGN.md "Audio front and back end") -----------------------------
+_AUDIO_TABLES = {}
+
+
+def stft_tables(n_fft, device):
+    """The device twiddle / window table of one n_fft (filled on the host in float64, cached per device)."""
+    key = (int(n_fft), torch.device(device).index)
+    t = _AUDIO_TABLES.get(key)
+    if t is None:
+        n = L.load().ldm_stft_table_floats(int(n_fft))
+        host = torch.empty(max(int(n), 1), dtype=torch.float32)
+        L.call("ldm_stft_fill_tables", int(n_fft), host.data_ptr())   # raises on an unsupported n_fft
+        t = _AUDIO_TABLES[key] = host.to(device)
+    return t
+
+
+def stft(y, n_fft=2048, hop_length=None, out="complex"):
+    """y [B, L] -> [B, F, T]: complex64 (out="complex"), |S| ("mag") or |S|^2 ("power")."""
+    require_device(y, dtype=None, what="stft")
+    y = f32c(y)
+    B, Ln = y.shape
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    tab = stft_tables(n_fft, y.device) if n_fft in (512, 2048) else y   # the C side names a bad n_fft
+    F, T = n_fft // 2 + 1, 1 + Ln // max(hop, 1)
+    if out == "complex":
+        S = torch.empty((B, F, T), device=y.device, dtype=torch.complex64)
+        L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), S.data_ptr(), None, 0, stream_handle())
+        return S
+    mag = torch.empty((B, F, T), device=y.device, dtype=torch.float32)
+    L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), None, mag.data_ptr(),
+           {"mag": 1, "power": 2}[out], stream_handle())
+    return mag
+
+
+def istft(S, length=None, n_fft=2048, hop_length=None, mag=None):
+    """S [B, F, T] complex64 (times mag [B, F, T] when given) -> y [B, length]; length defaults to (T - 1) * hop."""
+    require_device(S, dtype=torch.complex64, what="istft")
+    S = S.contiguous()
+    B, F, T = S.shape
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    if F != n_fft // 2 + 1:
+        raise RuntimeError(f"istft: {F} bins do not match n_fft {n_fft}")
+    tab = stft_tables(n_fft, S.device) if n_fft in (512, 2048) else S
+    Ln = (T - 1) * hop if length is None else int(length)
+    if mag is not None:
+        require_device(mag, what="istft")
+        mag = mag.contiguous()
+    y = torch.empty((B, Ln), device=S.device, dtype=torch.float32)
+    L.call("ldm_istft", S.data_ptr(), None if mag is None else mag.data_ptr(), y.data_ptr(), B, T, Ln, n_fft, hop,
+           tab.data_ptr(), stream_handle())
+    return y
+
+
+def griffinlim(mag, init_angles, n_iter, momentum, length, n_fft, hop_length=None):
+    """The Griffin-Lim loop (ldm_griffinlim) from init_angles [B, F, T] complex64; returns y [B, length]."""
+    require_device(mag, what="griffinlim")
+    require_device(init_angles, dtype=torch.complex64, what="griffinlim")
+    mag, init_angles = mag.contiguous(), init_angles.contiguous()
+    B, F, T = mag.shape
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    if F != n_fft // 2 + 1 or tuple(init_angles.shape) != (B, F, T):
+        raise RuntimeError("griffinlim: mag / init_angles shapes do not match n_fft")
+    tab = stft_tables(n_fft, mag.device) if n_fft in (512, 2048) else mag
+    ws = torch.empty(max(int(L.load().ldm_griffinlim_workspace(B, n_fft, T)), 1), device=mag.device,
+                     dtype=torch.float32)
+    y = torch.empty((B, int(length)), device=mag.device, dtype=torch.float32)
+    L.call("ldm_griffinlim", mag.data_ptr(), init_angles.data_ptr(), y.data_ptr(), B, T, int(length), n_fft, hop,
+           int(n_iter), float(momentum), tab.data_ptr(), ws.data_ptr(), stream_handle())
+    return y
+
+
+def mel_project(P, M, lohi):
+    """mel [B, n_mels, T] = M [n_mels, F] . P [B, F, T]; lohi int32 [n_mels, 2]: each filter's bin range."""
+    require_device(P, M, what="mel_project")
+    P = P.contiguous()
+    B, F, T = P.shape
+    mel = torch.empty((B, M.shape[0], T), device=P.device, dtype=torch.float32)
+    L.call("ldm_mel_project", P.data_ptr(), M.data_ptr(), lohi.data_ptr(), mel.data_ptr(), B, F, M.shape[0], T,
+           stream_handle())
+    return mel
+
+
+def power_to_db(x, amin=1e-10, top_db=80.0):
+    """Per item of x [B, ...]: 10 log10(max(x, amin)) referred to the item's own maximum, clamped at -top_db."""
+    require_device(x, dtype=None, what="power_to_db")
+    x = f32c(x)
+    B = x.shape[0]
+    out = torch.empty_like(x)
+    ws = torch.empty(B, device=x.device, dtype=torch.float32)
+    L.call("ldm_power_to_db", x.data_ptr(), out.data_ptr(), B, x.numel() // B, float(amin),
+           -1.0 if top_db is None else float(top_db), ws.data_ptr(), stream_handle())
+    return out
+
+
+def db_to_power(db):
+    require_device(db, dtype=None, what="db_to_power")
+    db = f32c(db)
+    out = torch.empty_like(db)
+    L.call("ldm_db_to_power", db.data_ptr(), out.data_ptr(), db.numel(), stream_handle())
+    return out
+
+
+def mel_invert(mel, M, Mt, Minv, lohi, inv_lambda, iters, take_sqrt=True):
+    """x [B, F, T] of ldm_mel_invert (projected-gradient non-negative least squares from the pseudo-inverse)."""
+    require_device(mel, M, Mt, Minv, what="mel_invert")
+    mel = mel.contiguous()
+    B, n_mels, T = mel.shape
+    F = M.shape[1]
+    x = torch.empty((B, F, T), device=mel.device, dtype=torch.float32)
+    ws = torch.empty((B, n_mels, T), device=mel.device, dtype=torch.float32)
+    L.call("ldm_mel_invert", mel.data_ptr(), M.data_ptr(), Mt.data_ptr(), Minv.data_ptr(), lohi.data_ptr(),
+           float(inv_lambda), int(iters), int(bool(take_sqrt)), x.data_ptr(), ws.data_ptr(), B, F, n_mels, T,
+           stream_handle())
+    return x
