@@ -411,6 +411,29 @@ int ldm_mel_invert(const float* mel, const float* M, const float* Mt, const floa
                    float inv_lambda, int32_t iters, int32_t take_sqrt, float* x, float* workspace, int32_t B,
                    int32_t F, int32_t n_mels, int32_t T, void* stream);
 
+/* ---- resampling and silence trim (resample.hip) -------------------------------------------
+ * The rational polyphase resampler  y[n] = sum_{j=-W..W} x[i0 + j] * taps[p][j + W],  i0 = floor(n down / up),
+ * p = (n down) mod up, x zero outside [0, L); taps [up, 2W+1] fp32 on the device is the caller's filter (the
+ * project's Kaiser-windowed sinc: ldm_amd.audio.resample_taps).  up / down is the reduced ratio sr_out / sr_in.
+ * The output has ldm_resample_out_len(L, up, down) = ceil(L up / down) samples per row (0 for bad arguments).
+ * One launch, no atomics, every output summed in ascending j: bitwise repeatable and independent of B.
+ * ldm_resample_f32: x [B, L] -> y [B, n_out].  ldm_resample_pcm16: interleaved int16 pcm [L, channels] -> y [n_out],
+ * each frame decoded as the mean over channels of s / 32768 in the load (bitwise the float form of that signal for
+ * 1 and 2 channels).  Ratios whose tile does not fit (up > 1024, or about 4 down + 2 W > 8192) are refused.
+ * ldm_trim_bounds: librosa.effects.trim's bounds per row of y [B, L]: frames t < 1 + L / hop cover
+ * [t hop - frame_length/2, t hop + frame_length/2) with zero padding, ms[t] their mean square; a frame is
+ * non-silent when max(ms[t], 1e-10) > max(max_t ms, 1e-10) * 10^(-top_db / 10); bounds[b] = {hop * first,
+ * min(L, hop * (last + 1))} as int64 on the device, {0, 0} when no frame passes or max_t ms <= 1e-10.
+ * workspace: ldm_trim_workspace_floats(B, L, hop) floats.  Two launches, no host synchronisation. */
+int64_t ldm_resample_out_len(int64_t L, int32_t up, int32_t down);
+int ldm_resample_f32(const float* x, int32_t B, int64_t L, const float* taps, int32_t up, int32_t down, int32_t W,
+                     float* y, void* stream);
+int ldm_resample_pcm16(const int16_t* pcm, int64_t L, int32_t channels, const float* taps, int32_t up, int32_t down,
+                       int32_t W, float* y, void* stream);
+int64_t ldm_trim_workspace_floats(int32_t B, int64_t L, int32_t hop);
+int ldm_trim_bounds(const float* y, int32_t B, int64_t L, int32_t frame_length, int32_t hop, float top_db,
+                    float* workspace, int64_t* bounds, void* stream);
+
 /* ---- step kernels (uconv.hip): fixed-structure implicit GEMMs of the nine UNet convs -------------------
  * Packed size (floats) of layer `layer` (0..8 = enc1..dec1) and its packing from the torch weight layout
  * (conv [Cout][Cin][3][3], transposed conv [Cin][Cout][3][3]).  ldm_step_conv runs one layer on NHWC

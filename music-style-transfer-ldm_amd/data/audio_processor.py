@@ -8,8 +8,9 @@ given a numpy array they run the reference's numpy code.
 The audio steps (mel spectrogram, STFT, Griffin-Lim) are librosa calls in the reference.  Here a CUDA tensor runs
 the native kernels (ldm_amd/audio.py, csrc/audio.hip) and returns CUDA tensors; a numpy array goes to librosa
 when it is importable, else through the native path when a HIP device is present (numpy out); with neither the
-method raises ImportError naming librosa.  load_audio falls back to the standard library's wave reader (PCM16 /
-float32, no resampling); trim_silence stays librosa-only.
+method raises ImportError naming librosa.  trim_silence follows the same rule (ldm_amd.audio.trim).  load_audio
+falls back to a RIFF reader (PCM16 / float32) and refuses a file at another rate; load_audio_native reads the same
+files at any rate and resamples them to target_sr on the GPU (ldm_amd.audio.resample / resample_pcm16).
 """
 import os
 import sys
@@ -66,8 +67,8 @@ def _out(t, as_numpy):
     return t.cpu().numpy() if as_numpy else t
 
 
-def read_wav(filepath):
-    """(float32 samples [frames, channels] in [-1, 1), rate) of a PCM16 or float32 .wav file."""
+def read_wav_raw(filepath):
+    """(samples [frames, channels] as stored: int16 PCM or float32, rate) of a PCM16 or float32 .wav file."""
     with open(filepath, "rb") as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
@@ -87,12 +88,20 @@ def read_wav(filepath):
         raise ValueError(f"{filepath}: missing fmt or data chunk")
     tag, ch, rate, _, _, bits = fmt
     if tag == 1 and bits == 16:
-        x = np.frombuffer(data, dtype="<i2").astype(np.float32) / 32768.0
+        x = np.frombuffer(data[:len(data) // 2 * 2], dtype="<i2").astype(np.int16)
     elif tag == 3 and bits == 32:
-        x = np.frombuffer(data, dtype="<f4").astype(np.float32)
+        x = np.frombuffer(data[:len(data) // 4 * 4], dtype="<f4").astype(np.float32)
     else:
         raise ValueError(f"{filepath}: only PCM16 and float32 .wav are read (format tag {tag}, {bits} bits)")
     return x[:len(x) // ch * ch].reshape(-1, ch), rate
+
+
+def read_wav(filepath):
+    """(float32 samples [frames, channels] in [-1, 1), rate) of a PCM16 or float32 .wav file."""
+    x, rate = read_wav_raw(filepath)
+    if x.dtype == np.int16:
+        x = x.astype(np.float32) / 32768.0
+    return x, rate
 
 
 def save_wav(path, audio, sr):
@@ -122,9 +131,28 @@ class AudioPreprocessor:
                              "resampling is unsupported without librosa")
         return x.mean(axis=1, dtype=np.float32), rate
 
+    def load_audio_native(self, filepath, device="cuda"):
+        """(CUDA float32 mono [L'], target_sr) of a PCM16 or float32 .wav at any rate: PCM16 travels to the device as
+        int16 and is decoded and mixed inside the resampler, float32 is mixed on the host and uploaded as float."""
+        import torch
+        from ldm_amd import audio
+        x, rate = read_wav_raw(filepath)
+        if x.shape[0] == 0:
+            raise ValueError(f"{filepath}: no samples")
+        if x.dtype == np.int16 and rate != self.target_sr:
+            return audio.resample_pcm16(torch.from_numpy(x).to(device), rate, self.target_sr), self.target_sr
+        if x.dtype == np.int16:
+            x = x.astype(np.float32) / 32768.0
+        y = torch.from_numpy(x.mean(axis=1, dtype=np.float32)).to(device)
+        return audio.resample(y, rate, self.target_sr), self.target_sr
+
     save_wav = staticmethod(save_wav)
 
     def trim_silence(self, audio, top_db=20):
+        nat = _native(audio)
+        if nat is not None:
+            A, y, as_np = nat
+            return _out(A.trim(y, top_db=top_db)[0], as_np)
         trimmed, _ = _librosa().effects.trim(audio, top_db=top_db)
         return trimmed
 

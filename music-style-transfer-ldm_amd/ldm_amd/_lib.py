@@ -119,6 +119,12 @@ SIGNATURES = {
     "ldm_db_to_power": (c_int32, [c_fp, c_fp, c_int64, c_vp]),
     "ldm_mel_invert": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_vp, c_float, c_int32, c_int32, c_fp, c_fp, c_int32,
                                  c_int32, c_int32, c_int32, c_vp]),
+    # resampling and silence trim (resample.hip)
+    "ldm_resample_out_len": (c_int64, [c_int64, c_int32, c_int32]),
+    "ldm_resample_f32": (c_int32, [c_fp, c_int32, c_int64, c_fp, c_int32, c_int32, c_int32, c_fp, c_vp]),
+    "ldm_resample_pcm16": (c_int32, [c_vp, c_int64, c_int32, c_fp, c_int32, c_int32, c_int32, c_fp, c_vp]),
+    "ldm_trim_workspace_floats": (c_int64, [c_int32, c_int64, c_int32]),
+    "ldm_trim_bounds": (c_int32, [c_fp, c_int32, c_int64, c_int32, c_int32, c_float, c_fp, c_vp, c_vp]),
     "ldm_batchnorm_train": (c_int32, [c_fp, c_int32, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_float, c_float,
                                       c_int32, c_fp, c_fp, c_fp, c_vp]),
     "ldm_batchnorm_train_out": (c_int32, [c_fp, c_fp, c_int32, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_float,

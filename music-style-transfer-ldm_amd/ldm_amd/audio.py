@@ -7,8 +7,14 @@ Every function takes batched CUDA tensors ([B, L] waveforms, [B, F, T] spectra, 
 current stream.  The filterbank, its pseudo-inverse and the step size of the mel inversion are float64 host
 computations, cached.  The mel inversion is this project's own: librosa's L-BFGS-B NNLS of an
 underdetermined system is not reproducible by another solver.
+
+In front of the transforms (csrc/resample.hip): resample / resample_pcm16, a rational polyphase
+Kaiser-windowed-sinc resampler that is this project's own definition (librosa's default, soxr_hq, cannot be
+reproduced offline), trim, librosa.effects.trim's algorithm, and chunk_mel_images, the dataset builder's batch of
+8-bit log-mel images.
 """
 import functools
+import math
 
 import numpy as np
 import torch
@@ -161,3 +167,83 @@ def griffinlim(mag, n_iter=32, momentum=0.99, seed=None, length=None, n_fft=None
 def mel_to_audio(mel, sr=SR, n_fft=N_FFT, n_iter=32, nnls_iters=32, momentum=0.99, seed=None, length=None):
     """Waveform [B, (T - 1) * hop] of a mel power spectrogram [B, n_mels, T]: mel_to_stft, then griffinlim."""
     return griffinlim(mel_to_stft(mel, sr, n_fft, nnls_iters), n_iter, momentum, seed, length, n_fft)
+
+
+# ---- resampling, silence trim, chunk images (csrc/resample.hip; DESIGN.md §7b) -------------------------------
+RESAMPLE_ZEROS, RESAMPLE_BETA, RESAMPLE_ROLLOFF = 32, 14.769656459379492, 0.945
+
+
+@functools.lru_cache(maxsize=None)
+def resample_taps(sr_in, sr_out):
+    """(up, down, W, table): the polyphase filter of sr_in -> sr_out as a read-only float64 table [up, 2W+1],
+    table[p, j + W] = h(j - p / up) with h(t) = fc sinc(fc t) I0(beta sqrt(1 - (t fc / Z)^2)) / I0(beta) on
+    |t| <= Z / fc (0 outside), fc = min(1, up / down) * rolloff, W = ceil(Z / fc), up / down = sr_out / sr_in reduced."""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in < 1 or sr_out < 1:
+        raise ValueError(f"resample_taps: sample rates must be positive ({sr_in}, {sr_out})")
+    g = math.gcd(sr_in, sr_out)
+    up, down = sr_out // g, sr_in // g
+    Z, fc = RESAMPLE_ZEROS, min(1.0, up / down) * RESAMPLE_ROLLOFF
+    W = int(math.ceil(Z / fc))
+    t = np.arange(-W, W + 1, dtype=np.float64)[None, :] - np.arange(up, dtype=np.float64)[:, None] / up
+    u = t * fc / Z
+    inside = np.abs(t) <= Z / fc
+    win = np.i0(RESAMPLE_BETA * np.sqrt(np.clip(1.0 - u * u, 0.0, None))) / np.i0(RESAMPLE_BETA)
+    table = np.where(inside, fc * np.sinc(fc * t) * win, 0.0)
+    table.setflags(write=False)
+    return up, down, W, table
+
+
+_TAPS_DEV = {}
+
+
+def _taps_device(sr_in, sr_out, device):
+    key = (int(sr_in), int(sr_out), torch.device(device).index)
+    v = _TAPS_DEV.get(key)
+    if v is None:
+        up, down, W, table = resample_taps(sr_in, sr_out)
+        v = _TAPS_DEV[key] = (up, down, W, torch.from_numpy(table.astype(np.float32)).to(device))
+    return v
+
+
+def resample(y, sr_in, sr_out):
+    """y [B, L] (or [L]) at sr_in -> [B, ceil(L up / down)] at sr_out; equal rates return y unchanged."""
+    if int(sr_in) == int(sr_out):
+        return y
+    y, one = _batched(y, 2)
+    ops.require_device(y, dtype=None, what="resample")
+    up, down, W, taps = _taps_device(sr_in, sr_out, y.device)
+    out = ops.resample(ops.f32c(y), taps, up, down, W)
+    return out[0] if one else out
+
+
+def resample_pcm16(pcm, sr_in, sr_out):
+    """Interleaved int16 PCM [L, ch] (or mono [L]) at sr_in -> mono float32 [ceil(L up / down)] at sr_out: each frame is
+    the mean over channels of s / 32768 (read_wav followed by .mean(axis=1)), decoded inside the resampler's load."""
+    if pcm.dim() == 1:
+        pcm = pcm.unsqueeze(1)
+    up, down, W, taps = _taps_device(sr_in, sr_out, pcm.device)
+    return ops.resample_pcm16(pcm, taps, up, down, W)
+
+
+def trim(y, top_db=20, frame_length=2048, hop_length=512):
+    """librosa.effects.trim: (y[start:end], (start, end)) for y [L] (one host read of the bounds, to slice); for
+    y [B, L] the int64 bounds tensor [B, 2] on the device, without a host synchronisation.  A row whose loudest frame
+    has a mean square <= 1e-10 (digital silence) is (0, 0)."""
+    if y.dim() == 2:
+        return ops.trim_bounds(y, top_db, frame_length, hop_length)
+    start, end = (int(v) for v in ops.trim_bounds(y.unsqueeze(0), top_db, frame_length, hop_length)[0].tolist())
+    return y[start:end], (start, end)
+
+
+def chunk_mel_images(y, sr, chunk_size, n_mels=128, max_db=80):
+    """uint8 [ceil(L / chunk_size), n_mels, 1 + chunk_size // 512]: y [L] cut into chunks of chunk_size samples (the
+    last zero-padded), each chunk's log-mel (power_to_db referred to the chunk's own maximum) as 8-bit pixels; one
+    batch through melspectrogram, power_to_db and ops.mel_quantize."""
+    ops.require_device(y, dtype=None, what="chunk_mel_images")
+    chunk_size = int(chunk_size)
+    if y.dim() != 1 or y.numel() == 0 or chunk_size < 1:
+        raise ValueError("chunk_mel_images: y must be a non-empty [L] waveform and chunk_size positive")
+    n = -(-y.numel() // chunk_size)
+    y = torch.nn.functional.pad(ops.f32c(y), (0, n * chunk_size - y.numel())).reshape(n, chunk_size)
+    return ops.mel_quantize(power_to_db(melspectrogram(y, sr=sr, n_mels=n_mels)), max_db)

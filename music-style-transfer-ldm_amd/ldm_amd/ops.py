@@ -1152,3 +1152,51 @@ def mel_invert(mel, M, Mt, Minv, lohi, inv_lambda, iters, take_sqrt=True):
            float(inv_lambda), int(iters), int(bool(take_sqrt)), x.data_ptr(), ws.data_ptr(), B, F, n_mels, T,
            stream_handle())
     return x
+
+
+# ---- resampling and silence trim (resample.hip) ----------------------------------------------
+def _resample_out(name, rows, Ln, up, down, device):
+    n_out = int(L.load().ldm_resample_out_len(int(Ln), int(up), int(down)))
+    if n_out <= 0:
+        raise RuntimeError(f"{name}: bad length or ratio (L {Ln}, up {up}, down {down})")
+    return torch.empty((rows, n_out), device=device, dtype=torch.float32)
+
+
+def resample(x, taps, up, down, W):
+    """x [B, L] fp32 -> [B, ceil(L up / down)] through the polyphase table taps [up, 2W+1] (device fp32)."""
+    require_device(x, taps, what="resample")
+    x = x.contiguous()
+    B, Ln = x.shape
+    if tuple(taps.shape) != (up, 2 * W + 1) or not taps.is_contiguous():
+        raise RuntimeError(f"resample: taps must be a contiguous [{up}, {2 * W + 1}] table")
+    y = _resample_out("resample", B, Ln, up, down, x.device)
+    L.call("ldm_resample_f32", x.data_ptr(), B, Ln, taps.data_ptr(), int(up), int(down), int(W), y.data_ptr(),
+           stream_handle())
+    return y
+
+
+def resample_pcm16(pcm, taps, up, down, W):
+    """Interleaved int16 pcm [L, ch] -> mono fp32 [ceil(L up / down)]: decoded and mixed in the kernel's load."""
+    require_device(pcm, dtype=torch.int16, what="resample_pcm16")
+    require_device(taps, what="resample_pcm16")
+    pcm = pcm.contiguous()
+    Ln, ch = pcm.shape
+    if tuple(taps.shape) != (up, 2 * W + 1) or not taps.is_contiguous():
+        raise RuntimeError(f"resample_pcm16: taps must be a contiguous [{up}, {2 * W + 1}] table")
+    y = _resample_out("resample_pcm16", 1, Ln, up, down, pcm.device)
+    L.call("ldm_resample_pcm16", pcm.data_ptr(), Ln, ch, taps.data_ptr(), int(up), int(down), int(W), y.data_ptr(),
+           stream_handle())
+    return y[0]
+
+
+def trim_bounds(y, top_db=20.0, frame_length=2048, hop_length=512):
+    """int64 [B, 2] on the device: librosa.effects.trim's (start, end) of each row of y [B, L]."""
+    require_device(y, dtype=None, what="trim_bounds")
+    y = f32c(y)
+    B, Ln = y.shape
+    ws = torch.empty(max(int(L.load().ldm_trim_workspace_floats(B, Ln, int(hop_length))), 1), device=y.device,
+                     dtype=torch.float32)
+    bounds = torch.empty((B, 2), device=y.device, dtype=torch.int64)
+    L.call("ldm_trim_bounds", y.data_ptr(), B, Ln, int(frame_length), int(hop_length), float(top_db), ws.data_ptr(),
+           bounds.data_ptr(), stream_handle())
+    return bounds
