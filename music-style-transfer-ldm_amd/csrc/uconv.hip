@@ -85,15 +85,32 @@ __host__ __device__ constexpr int tphase(int t) { return (tky(t) != 1 ? 2 : 0) +
 // offset) within a stage and reused by the other taps with that offset.  B_SRC<MODE, S>(i): the chunk of the
 // stage whose fragment chunk i uses (i itself when it loads).
 __host__ __device__ constexpr int toff(int t) { return (tky(t) == 0 ? 2 : 0) + (tkx(t) == 0 ? 1 : 0); }
-template <int MODE>
+// Tap classes of the transposed layers (TC; 0: all nine taps).  Each tap feeds one output parity, so the taps split
+// into two classes with disjoint outputs: class 1 = the four taps of parity (odd, odd) (ky, kx in {0, 2}), class 2 =
+// the other five, which cover parities (even, even), (even, odd) and (odd, even) = tphase 0, 1, 2.  A block that
+// carries one class over ALL input channels finishes its parities by itself: no partial tile leaves the block.
+constexpr int kTapClass = -1;   // value of the kernels' KS slot: blocks = tiles x the two tap classes
+__host__ __device__ constexpr int tc_ntap(int TC) { return TC == 1 ? 4 : (TC == 2 ? 5 : 9); }
+__host__ __device__ constexpr int tc_tap(int TC, int i) {
+    return TC == 1 ? 6 * (i >> 1) + 2 * (i & 1) : (TC == 2 ? (i == 0 ? 1 : (i == 4 ? 7 : i + 2)) : i);
+}
+__host__ __device__ constexpr int tc_nph(int MODE, int TC) { return MODE != 2 ? 1 : (TC == 1 ? 1 : (TC == 2 ? 3 : 4)); }
+template <int MODE, int TC = 0>
 __host__ __device__ constexpr int b_src(int st, int S, int i) {
     if (MODE != 2) return i;
+    constexpr int CPC = tc_ntap(TC);
     const int c = st * S + i;
     for (int j = 0; j < i; ++j) {
         const int cj = st * S + j;
-        if (cj / 9 == c / 9 && toff(cj % 9) == toff(c % 9)) return j;
+        if (cj / CPC == c / CPC && toff(tc_tap(TC, cj % CPC)) == toff(tc_tap(TC, c % CPC))) return j;
     }
     return i;
+}
+// the first chunk of a channel chunk's taps that reads offset (0, 0), the lane's own position
+__host__ __device__ constexpr int tc_own(int TC) {
+    for (int i = 0; i < tc_ntap(TC); ++i)
+        if (toff(tc_tap(TC, i)) == 0) return i;
+    return -1;
 }
 
 // Diagnostic builds only (never shipped; tools/step_diag.sh): UCONV_DIAG bit 0 = no MFMAs, bit 1 = no
@@ -130,14 +147,15 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-template <int MODE, int CIN, int COUT, int TM, int TN, int WN, int WK, int NCH, int S, int EPI, int DT, int KS>
+template <int MODE, int CIN, int COUT, int TM, int TN, int WN, int WK, int NCH, int S, int EPI, int DT, int KS, int TC = 0>
 __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
-    constexpr int NPH = MODE == 2 ? 4 : 1;
+    constexpr int NPH = tc_nph(MODE, TC);         // accumulator sets: the output parities this block finishes
     constexpr int NST = NCH / S;
-    constexpr int CPC = 9;                        // chunks per channel chunk (the 9 taps)
+    constexpr int CPC = tc_ntap(TC);              // chunks per channel chunk (the 9 taps, or the taps of class TC)
     static_assert(NCH % S == 0 && NCH % CPC == 0, "stage / chunk structure");
     static_assert(CIN % 16 == 0 && COUT % (16 * TM) == 0, "channel tiling");
-    static_assert((9 * CIN / 16) == NCH * WK * KS, "the grid's waves cover K exactly once");
+    static_assert(CIN / 16 == (NCH / CPC) * WK * KS, "the grid's waves cover K exactly once");
+    static_assert(TC == 0 || (MODE == 2 && KS == 1 && (EPI & EPI_PLANE) != 0), "tap classes: transposed plane form");
     // a lone accumulator chain of 16x16x4 (40-cycle dependent latency, 32-cycle issue) alternates two
     constexpr int NACC2 = (NPH * TM * TN == 1) ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -219,7 +237,7 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
         __builtin_amdgcn_make_buffer_rsrc(uni_ptr(a.w), (short)0, WBYTES, 0x00020000);
     const int va = ((m0 + col) * 16 + lg * 4) * AE;            // A: row m0+col, k-local 4*lg .. +3
     const int kw0 = ks * WK + wk;                              // this wave's slice of K
-    const int sa0 = uni(kw0 * NCH * COUT * 16 * AE);           // first chunk of this wave
+    const int sa0 = uni(kw0 * (NCH / CPC) * 9 * COUT * 16 * AE);   // first chunk (tap 0) of its first channel chunk
     const int sb0 = uni(kw0 * (NCH / CPC) * 64);               // its first channel chunk (16 ch x 4 B)
 
     floatx4 acc[NACC2][NPH][TM][TN];
@@ -243,11 +261,12 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
         static_for<0, S>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             constexpr int c = st * S + i;                 // chunk within this wave's range
-            constexpr int t = c % CPC, cc = c / CPC;
+            constexpr int t = tc_tap(TC, c % CPC), cc = c / CPC;
+            constexpr int cw = cc * 9 + t;                // ... and within the wave's packed weights
             if constexpr ((PART & 1) != 0)
 #pragma unroll
             for (int mi = 0; mi < TM; ++mi) {
-                const int so = sa0 + (c * COUT * 16 + mi * 256) * AE;
+                const int so = sa0 + (cw * COUT * 16 + mi * 256) * AE;
                 if constexpr ((UCONV_DIAG & 2) != 0)
                     fa[bf][i][mi] = AT{};
                 else if constexpr (DT != 0)
@@ -255,7 +274,7 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
                 else
                     fa[bf][i][mi] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(wr, va, so, 0));
             }
-            if constexpr ((PART & 2) != 0 && b_src<MODE>(st, S, i) == i)
+            if constexpr ((PART & 2) != 0 && b_src<MODE, TC>(st, S, i) == i)
 #pragma unroll
             for (int ni = 0; ni < TN; ++ni)
                 fb[bf][i][ni] = (UCONV_DIAG & 2) ? floatx4{(float)vt[t][ni], 1.f, 2.f, 3.f}
@@ -270,8 +289,9 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
         static_for<0, S>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             constexpr int c = st * S + i;
-            constexpr int p = MODE == 2 ? tphase(c % CPC) : 0;
-            constexpr int ib = b_src<MODE>(st, S, i);   // the fragment this chunk's taps share
+            // (class 1 has the one parity 3 = set 0; class 2's parities are tphase 0..2, its sets in that order)
+            constexpr int p = MODE == 2 && TC != 1 ? tphase(tc_tap(TC, c % CPC)) : 0;
+            constexpr int ib = b_src<MODE, TC>(st, S, i);   // the fragment this chunk's taps share
             if constexpr (DT != 0) {   // fp16 / bf16 operands: the whole 16-channel chunk in one MFMA
                 constexpr int u = NACC2 == 2 ? (c & 1) : 0;
 #pragma unroll
@@ -318,7 +338,7 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
     };
     auto out_of = [&](int f) {
         const int fc = f < NFR ? f : NFR - 1;
-        const int p = fc / (TM * TN), mi = (fc / TN) % TM, ni = fc % TN;
+        const int p = TC == 1 ? 3 : fc / (TM * TN), mi = (fc / TN) % TM, ni = fc % TN;   // p: the output parity
         Out o;
         o.b = colsel(cb, ni);
         o.oy = MODE == 2 ? 2 * colsel(cqy, ni) + (p >> 1) : colsel(cqy, ni);
@@ -405,13 +425,15 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
     } else if constexpr (PLANE && MODE == 2) {
         // transposed conv over a 2 x 8 input plane: the four offsets a tap reads, (qy + oy, qx + ox) with oy, ox in
         // {0, 1}, are all in the sample's own plane (zero past its last row / column): one load per channel chunk
+        // (OWN: the slot of the first tap in the list that reads offset (0, 0))
         constexpr int NCC = S / CPC;
+        constexpr int OWN = tc_own(TC);
         static_for<0, NCC>([&](auto ccc) {
             constexpr int cc = decltype(ccc)::value;
 #pragma unroll
             for (int ni = 0; ni < TN; ++ni)   // tap 8 = (2, 2) reads offset (0, 0): the lane's own position
-                fb[0][cc * CPC + 4][ni] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                                          xr, vt[8][ni], sb0 + cc * 64, XAUX));
+                fb[0][cc * CPC + OWN][ni] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                                            xr, vt[8][ni], sb0 + cc * 64, XAUX));
         });
         __builtin_amdgcn_sched_barrier(0);
         load_stage(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
@@ -424,15 +446,15 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
             constexpr int cc = decltype(ccc)::value;
 #pragma unroll
             for (int ni = 0; ni < TN; ++ni)
-                *reinterpret_cast<floatx4*>(win + ((cc * TN + ni) * 16 + col) * 16 + lg * 4) = fb[0][cc * CPC + 4][ni];
+                *reinterpret_cast<floatx4*>(win + ((cc * TN + ni) * 16 + col) * 16 + lg * 4) = fb[0][cc * CPC + OWN][ni];
         });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // cross-lane through LDS: see the stride-2 plane branch
         static_for<0, NCC>([&](auto ccc) {
             constexpr int cc = decltype(ccc)::value;
             static_for<0, CPC>([&](auto tc) {
-                constexpr int t = decltype(tc)::value;
-                constexpr int i = cc * CPC + t;
-                if constexpr (b_src<MODE>(0, S, i) == i) {
+                constexpr int t = tc_tap(TC, decltype(tc)::value);
+                constexpr int i = cc * CPC + decltype(tc)::value;
+                if constexpr (b_src<MODE, TC>(0, S, i) == i) {
                     constexpr int oy = tky(t) == 0 ? 1 : 0, ox = tkx(t) == 0 ? 1 : 0;
                     const bool in = py + oy < 2 && px + ox < 8;
 #pragma unroll
@@ -691,7 +713,18 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
 template <int MODE, int CIN, int COUT, int TM, int TN, int WN, int WK, int NCH, int S, int EPI, int DT, int KS = 1>
 __global__ __launch_bounds__(64 * WN * WK) __attribute__((amdgpu_waves_per_eu((WN * WK + 3) / 4, (WN * WK + 3) / 4)))
 void uconv_kernel(UArgs a) {
-    uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH, S, EPI, DT, KS>(a, blockIdx.x);
+    if constexpr (KS == kTapClass) {
+        // blocks [0, tiles): tap class 1, [tiles, 2 tiles): class 2 — the two blocks of a tile are a whole number of
+        // XCD rounds apart (tile counts that are multiples of 8), so they read the tile's activations from one L2.
+        // NCH / S are class 2's chunk counts (5 taps per channel chunk); class 1 runs 4 per channel chunk.
+        const int tiles = a.nMt * a.nNt;
+        if ((int)blockIdx.x < tiles)
+            uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH / 5 * 4, S / 5 * 4, EPI, DT, 1, 1>(a, blockIdx.x);
+        else
+            uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH, S, EPI, DT, 1, 2>(a, (int)blockIdx.x - tiles);
+    } else {
+        uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH, S, EPI, DT, KS>(a, blockIdx.x);
+    }
 }
 
 // packed[c][m][16], c = cc*9 + t, element e = 4*lg + j  ->  input channel cc*16 + e, tap t = ky*3 + kx.
@@ -750,15 +783,17 @@ struct LayerGeo {
 
 template <int MODE, int CIN, int COUT, int TM, int TN, int WN, int WK, int NCH, int S, int EPI, int DT, int KS>
 static int launch_dt(const UArgs& a, hipStream_t st) {
-    constexpr int NPH = MODE == 2 ? 4 : 1;
-    const int blocks = a.nMt * a.nNt * KS;
+    // (tap classes: sized for class 2, the larger of the two: three parities, S / 5 channel chunks per wave)
+    constexpr int NPH = KS == kTapClass ? tc_nph(MODE, 2) : tc_nph(MODE, 0);
+    constexpr int NCC = KS == kTapClass ? S / 5 : S / 9;
+    const int blocks = a.nMt * a.nNt * (KS == kTapClass ? 2 : KS);
     size_t lds = std::max<size_t>(WK > 1 ? (size_t)WK * WN * NPH * TM * TN * 64 * 16 : 0, KS > 1 ? 16 : 0);
     if constexpr ((EPI & EPI_PLANE) != 0)   // + each wave's activation window (see EPI_PLANE; 4 KB per sample at stride 2)
-        lds = (WK > 1 ? (size_t)WK * WN * NPH * TM * TN * 64 * 16 : 0) + (size_t)WN * WK * (S / 9) * TN * (MODE == 1 ? 4096 : 1024);
+        lds = (WK > 1 ? (size_t)WK * WN * NPH * TM * TN * 64 * 16 : 0) + (size_t)WN * WK * NCC * TN * (MODE == 1 ? 4096 : 1024);
     if constexpr ((EPI & EPI_WINDOW) != 0) {   // + each wave's row window (see EPI_WINDOW)
         constexpr int WR = MODE == 2 ? 2 : 3;
         constexpr int WC = MODE == 0 ? 16 * TN + 2 : (MODE == 1 ? 32 * TN + 1 : 16 * TN + 1);
-        lds = (WK > 1 ? (size_t)WK * WN * NPH * TM * TN * 64 * 16 : 0) + (size_t)WN * WK * (S / 9) * WR * WC * 64;
+        lds = (WK > 1 ? (size_t)WK * WN * NPH * TM * TN * 64 * 16 : 0) + (size_t)WN * WK * NCC * WR * WC * 64;
     }
     auto kfn = uconv_kernel<MODE, CIN, COUT, TM, TN, WN, WK, NCH, S, EPI, DT, KS>;
     if (lds > 64 * 1024) {   // dynamic LDS past 64 KiB needs the per-function opt-in, once
@@ -822,13 +857,17 @@ constexpr KsGeo kKs2[9] = {
 // 71.41-71.71, + dec3 71.44-71.56, + dec2 72.34-72.50, all six 70.12-70.18 (gpurun_out/r6b8); the fp16 loop
 // 57.97 -> 56.70-57.06 with enc4 + dec4, unchanged by the other four; + dec1 with its DDIM update 70.30-70.44 ->
 // 69.72-69.87, fp16 55.50-55.73 -> 55.19-55.23 (gpurun_out/r6b9).
+// Round 7: dec4's two blocks per tile split the taps by output parity (kTapClass, dec4_par()) instead of K: no
+// partial slabs, dec4 7.66 -> 6.35 us (rocprof average), WRITE 1.585 -> 0.524 MB per launch, the fp32 loop
+// 69.76-69.96 -> 68.94-69.24, fp16 55.16-55.42 -> 53.90-54.30 us per iteration (profiles/r07).  The K-split row
+// below stays selectable (LDM_UCONV_DEC4_PAR=0) and sizes the workspace.
 constexpr KsGeo kKs3[9] = {
     {2, 1, 2, 1, 4},   // enc1        32 x 64 tiles (4 wave columns), K (2 channel chunks) over 2 waves: 8 waves
     {2, 1, 4, 1, 2},   // enc2        32 x 32 tiles (2 wave columns of 16), K over 4 waves: 8 waves
     {2, 1, 8, 1},    // enc3        32 x 16 tiles, K over 8 waves
     {1, 1, 16, 1},   // enc4        256 tiles, K whole
     {0, 0, 0, 0},
-    {1, 1, 16, 2},   // dec4        128 tiles x 2
+    {1, 1, 16, 2},   // dec4        128 tiles x 2 (K halves; by default the two tap classes instead)
     {1, 1, 16, 1},   // dec3        256 tiles, K over 16 waves
     {1, 2, 8, 1},    // dec2        16 x 32 tiles, K over 8 waves
     {1, 2, 4, 1, 2}, // dec1 + DDIM 16 x 64 tiles (2 wave columns), K over 4 waves: 8 waves
@@ -965,6 +1004,15 @@ static bool plane_taps() {
     }();
     return on;
 }
+// dec4's wide form split over two blocks by tap class (kTapClass) instead of by K; LDM_UCONV_DEC4_PAR=0 keeps the
+// K-split instance (A/B timing)
+static bool dec4_par() {
+    static const bool on = [] {
+        const char* e = std::getenv("LDM_UCONV_DEC4_PAR");
+        return e ? std::atoi(e) != 0 : true;
+    }();
+    return on;
+}
 // spatial size divisor of each layer's input (model.py:178-194)
 constexpr int kDiv[9] = {1, 1, 2, 4, 8, 8, 4, 2, 1};
 static void ks_tiles(int layer, int B, int H, int W, int64_t& tiles, int64_t& slab_floats, int form = 1) {
@@ -984,7 +1032,8 @@ static void ks_tiles(int layer, int B, int H, int W, int64_t& tiles, int64_t& sl
 int step_ks_mask() {
     int m = uc::ks_mask();
     for (int l = 0; l < 9; ++l)
-        if (uc::kKs3[l].wk > 0 && ((uc::ks3_mask() >> l) & 1)) m = uc::kKs3[l].ks > 1 ? (m | (1 << l)) : (m & ~(1 << l));
+        if (uc::kKs3[l].wk > 0 && ((uc::ks3_mask() >> l) & 1))
+            m = uc::kKs3[l].ks > 1 && !(l == 5 && uc::dec4_par()) ? (m | (1 << l)) : (m & ~(1 << l));
     return m;
 }
 
@@ -1110,6 +1159,10 @@ int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st)
             case 3: LDM_REQUIRE(s.y && a.Hin == 4 && a.Win == 16 && plane_taps(), "enc4 (variant 3): y, 4 x 16 input plane");
                 return launch<1, 256, 512, 1, 1, 1, 16, 9, 9, EPI_RELU | EPI_POSB | EPI_PLANE, 1>(a, s.dtype, st);
             case 5: LDM_REQUIRE(s.y && s.skip && a.Hin == 2 && a.Win == 8 && plane_taps(), "dec4 (variant 3): y, skip, 2 x 8 plane");
+                if (dec4_par()) {   // no partial tiles: the workspace stays untouched
+                    a.slab = nullptr, a.cnt = nullptr;
+                    return launch<2, 512, 256, 1, 1, 1, 16, 10, 10, EPI_RELU | EPI_SKIP | EPI_PLANE, kTapClass>(a, s.dtype, st);
+                }
                 return launch<2, 512, 256, 1, 1, 1, 16, 9, 9, EPI_RELU | EPI_SKIP | EPI_PLANE, 2>(a, s.dtype, st);
             default: return fail(2, "step conv: no K-split variant 3 for this layer");
         }
