@@ -434,6 +434,25 @@ int64_t ldm_trim_workspace_floats(int32_t B, int64_t L, int32_t hop);
 int ldm_trim_bounds(const float* y, int32_t B, int64_t L, int32_t frame_length, int32_t hop, float top_db,
                     float* workspace, int64_t* bounds, void* stream);
 
+/* ---- whole-recording windows (longform.hip) ------------------------------------------------
+ * The window plan of a recording of T_total mel frames: N = max(1, ceil((T_total - overlap) / stride)) windows of
+ * `frames` frames, stride = frames - overlap; window n covers frames [n stride, n stride + frames), frames at or
+ * beyond T_total hold zero power.  frames is a multiple of 64 and 0 <= overlap <= frames / 2 (at most two windows
+ * cover a frame).  ldm_mel_window_count returns N, 0 for a bad plan.
+ * ldm_mel_windows: P [n_mels, T_total] mel power -> x [N, 1, n_mels, frames], the model's [0,1] input of each
+ * window, and ref_db [N] = 10 log10(max(amin, max of window n)); x is bitwise ldm_u8_to_unit(ldm_mel_quantize(
+ * ldm_power_to_db(window n, amin, top_db), max_db)) of the zero-padded window.  Two launches, no unfolded copy.
+ * ldm_mel_stitch: y [N, 1, n_mels, frames] decoded windows -> power [n_mels, T_total] = 10^(db / 10) and, when db
+ * is not null, db [n_mels, T_total]; with d(n, j) = clamp(y[n, 0, m, j], 0, 1) max_db - max_db + ref_db[n],
+ * n1 = min(N - 1, t / stride), j1 = t - n1 stride:  db = d(n1, j1), or inside an overlap (n1 >= 1, j1 < overlap)
+ * ((overlap - j1) d(n1 - 1, j1 + stride) + (j1 + 1) d(n1, j1)) / (overlap + 1).  N must be the plan's count.
+ * One launch, gather form, no atomics: bitwise repeatable. */
+int64_t ldm_mel_window_count(int64_t T_total, int32_t frames, int32_t overlap);
+int ldm_mel_windows(const float* P, int32_t n_mels, int64_t T_total, int32_t frames, int32_t overlap, float amin,
+                    float top_db, float max_db, float* x, float* ref_db, void* stream);
+int ldm_mel_stitch(const float* y, const float* ref_db, int32_t N, int32_t n_mels, int32_t frames, int32_t overlap,
+                   int64_t T_total, float max_db, float* power, float* db, void* stream);
+
 /* ---- step kernels (uconv.hip): fixed-structure implicit GEMMs of the nine UNet convs -------------------
  * Packed size (floats) of layer `layer` (0..8 = enc1..dec1) and its packing from the torch weight layout
  * (conv [Cout][Cin][3][3], transposed conv [Cin][Cout][3][3]).  ldm_step_conv runs one layer on NHWC

@@ -17,6 +17,7 @@
 // frames into an LDS tile [4][H+8] of float2 and stores / loads it with t fastest (32-byte runs; H+8 = 8 mod 32
 // keeps the four frames' ds_read_b64 on disjoint banks).
 #include "common.h"
+#include "mel_db.h"
 
 #include <cmath>
 #include <vector>
@@ -346,25 +347,22 @@ __global__ __launch_bounds__(1024) void db_ref_kernel(const float* __restrict__ 
         if ((int)threadIdx.x < w) s[threadIdx.x] = fmaxf(s[threadIdx.x], s[threadIdx.x + w]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) ref[blockIdx.x] = 10.0f * log10f(fmaxf(amin, s[0]));
+    if (threadIdx.x == 0) ref[blockIdx.x] = db_ref(s[0], amin);
 }
 
 __global__ __launch_bounds__(256) void power_to_db_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n,
                                                           float amin, float top_db, const float* __restrict__ ref) {
-#pragma clang fp contract(off)   // 10 log10(max) - ref must cancel exactly: the item's maximum is 0 dB
+#pragma clang fp contract(off)   // 10 log10(max) - ref must cancel exactly: the item's maximum is 0 dB (power_db1)
     const int b = blockIdx.y;
     const float r = ref[b];
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        float v = 10.0f * log10f(fmaxf(amin, x[(int64_t)b * n + i])) - r;
-        if (top_db >= 0.f) v = fmaxf(v, -top_db);   // the item's own maximum is 0 dB
-        out[(int64_t)b * n + i] = v;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[(int64_t)b * n + i] = power_db1(x[(int64_t)b * n + i], amin, top_db, r);
 }
 
 __global__ __launch_bounds__(256) void db_to_power_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = exp10f(0.1f * x[i]);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = db_power1(x[i]);
 }
 
 __global__ __launch_bounds__(256) void sqrt_kernel(float* __restrict__ x, int64_t n) {

@@ -3,21 +3,14 @@
 // [0,1] float tensors the model consumes (dataset.py:252-260, torchvision ToTensor).  Elementwise and
 // HBM-bound: one float4 / uchar4 per lane, grid-stride, the reference's fp32 operation order.
 #include "common.h"
+#include "mel_db.h"
 
 #pragma clang fp contract(off)
 
 namespace ldm {
 namespace {
 
-// uint8(clip((db + max_db) * (255 / max_db), 0, 255) + 0.5): numpy float32 arithmetic, truncating cast
-__device__ __forceinline__ unsigned char quant1(float v, float max_db, float scale) {
-    float s = v + max_db;
-    s = s * scale;
-    s = s < 0.f ? 0.f : (s > 255.f ? 255.f : s);
-    s = s + 0.5f;
-    return (unsigned char)(int)s;
-}
-
+// quant1 / unit1: the pixel arithmetic, mel_db.h
 __global__ __launch_bounds__(256) void mel_quantize_kernel(const float* __restrict__ db, unsigned char* __restrict__ out,
                                                            int64_t n, float max_db, float scale) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(256) void mel_dequantize_kernel(const unsigned char
 __global__ __launch_bounds__(256) void u8_to_unit_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
                                                          int64_t n) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (float)in[i] / 255.0f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = unit1(in[i]);
 }
 
 unsigned grid_for(int64_t n, int per_lane) {

@@ -125,6 +125,11 @@ SIGNATURES = {
     "ldm_resample_pcm16": (c_int32, [c_vp, c_int64, c_int32, c_fp, c_int32, c_int32, c_int32, c_fp, c_vp]),
     "ldm_trim_workspace_floats": (c_int64, [c_int32, c_int64, c_int32]),
     "ldm_trim_bounds": (c_int32, [c_fp, c_int32, c_int64, c_int32, c_int32, c_float, c_fp, c_vp, c_vp]),
+    # whole-recording windows (longform.hip)
+    "ldm_mel_window_count": (c_int64, [c_int64, c_int32, c_int32]),
+    "ldm_mel_windows": (c_int32, [c_fp, c_int32, c_int64, c_int32, c_int32, c_float, c_float, c_float, c_fp, c_fp,
+                                  c_vp]),
+    "ldm_mel_stitch": (c_int32, [c_fp, c_fp, c_int32, c_int32, c_int32, c_int32, c_int64, c_float, c_fp, c_fp, c_vp]),
     "ldm_batchnorm_train": (c_int32, [c_fp, c_int32, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_float, c_float,
                                       c_int32, c_fp, c_fp, c_fp, c_vp]),
     "ldm_batchnorm_train_out": (c_int32, [c_fp, c_fp, c_int32, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_float,

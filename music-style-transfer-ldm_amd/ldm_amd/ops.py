@@ -1154,6 +1154,50 @@ def mel_invert(mel, M, Mt, Minv, lohi, inv_lambda, iters, take_sqrt=True):
     return x
 
 
+# ---- whole-recording windows (longform.hip) --------------------------------------------------
+def _window_count(name, T_total, frames, overlap):
+    N = int(L.load().ldm_mel_window_count(int(T_total), int(frames), int(overlap)))
+    if N < 1:
+        raise RuntimeError(f"{name}: bad plan (T_total {T_total}, frames {frames}, overlap {overlap}): T_total >= 1, "
+                           "frames a multiple of 64 and 0 <= overlap <= frames / 2 are required")
+    return N
+
+
+def mel_windows(P, frames=512, overlap=64, max_db=80, amin=1e-10, top_db=80.0):
+    """P [n_mels, T_total] mel power -> (x [N, 1, n_mels, frames] in [0,1], ref_db [N]): each window's log-mel referred
+    to its own maximum as 8-bit levels / 255, bitwise u8_to_unit(mel_quantize(power_to_db(window))) (ldm_mel_windows)."""
+    require_device(P, dtype=None, what="mel_windows")
+    P = f32c(P)
+    if P.dim() != 2:
+        raise RuntimeError(f"mel_windows: expects one recording's [n_mels, T_total], got {tuple(P.shape)}")
+    n_mels, T = P.shape
+    N = _window_count("mel_windows", T, frames, overlap)
+    x = torch.empty((N, 1, n_mels, int(frames)), device=P.device, dtype=torch.float32)
+    ref_db = torch.empty(N, device=P.device, dtype=torch.float32)
+    L.call("ldm_mel_windows", P.data_ptr(), n_mels, T, int(frames), int(overlap), float(amin),
+           -1.0 if top_db is None else float(top_db), float(max_db), x.data_ptr(), ref_db.data_ptr(), stream_handle())
+    return x, ref_db
+
+
+def mel_stitch(y, ref_db, overlap, T_total, max_db=80, return_db=False):
+    """Decoded windows y [N, 1, n_mels, frames] and their ref_db [N] -> mel power [n_mels, T_total], crossfaded linearly
+    in dB over each overlap (ldm_mel_stitch); with return_db also the stitched dB map."""
+    require_device(y, ref_db, dtype=None, what="mel_stitch")
+    y, ref_db = f32c(y), f32c(ref_db)
+    if y.dim() != 4 or y.shape[1] != 1 or tuple(ref_db.shape) != (y.shape[0],):
+        raise RuntimeError(f"mel_stitch: expects y [N, 1, n_mels, frames] and ref_db [N], got {tuple(y.shape)} and "
+                           f"{tuple(ref_db.shape)}")
+    N, _, n_mels, frames = y.shape
+    if _window_count("mel_stitch", T_total, frames, overlap) != N:
+        raise RuntimeError(f"mel_stitch: {N} windows given, the plan of (T_total {T_total}, frames {frames}, overlap "
+                           f"{overlap}) has {_window_count('mel_stitch', T_total, frames, overlap)}")
+    power = torch.empty((n_mels, int(T_total)), device=y.device, dtype=torch.float32)
+    db = torch.empty_like(power) if return_db else None
+    L.call("ldm_mel_stitch", y.data_ptr(), ref_db.data_ptr(), N, n_mels, frames, int(overlap), int(T_total),
+           float(max_db), power.data_ptr(), _p(db), stream_handle())
+    return (power, db) if return_db else power
+
+
 # ---- resampling and silence trim (resample.hip; DESIGN.md §7b) ----------------------------------------------
 def _resample_out(name, rows, Ln, up, down, device):
     n_out = int(L.load().ldm_resample_out_len(int(Ln), int(up), int(down)))

@@ -1,0 +1,116 @@
+"""Style transfer of a whole recording: the content is cut into overlapping windows (ldm_amd.longform), every window
+goes through LDM.content_style_transfer_wrapper paired with a window of the style recording, and the decoded windows
+are crossfaded into one mel spectrogram that is vocoded once, so the phase is continuous across the seams.
+
+    python -m models.transfer --content a.wav --style b.wav --out c.wav [--checkpoint ldm.pth]
+
+The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
+"""
+import argparse
+import math
+from types import SimpleNamespace
+
+import torch
+
+from . import _pathfix  # noqa: F401
+from ldm_amd import audio, longform
+
+HOP = audio.N_FFT // 4
+
+
+def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, num_timesteps=100, eta=0.0,
+                       batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80):
+    """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
+    windows_out [N, 1, n_mels, frames], ref_db [N] and N.
+
+    Call model.eval() first: the decoder's train-mode BatchNorm takes its statistics over the batch, which couples
+    the windows of a group and makes the result depend on batch_size.  This function leaves module modes alone.
+
+    Content window n is paired with style window n mod Ns, Ns the style's full windows (overlap 0; its single padded
+    window when it has no full one).  The q_sample noise of window n is row n of one CPU draw seeded with `seed`,
+    whatever batch_size is.  ValueError for a recording shorter than n_fft / 2 + 1 samples, a bad window plan, or
+    num_timesteps beyond the model's schedule."""
+    n_mels = 128
+    for name, y in (("content", content), ("style", style)):
+        if y.dim() != 1 or y.numel() < audio.N_FFT // 2 + 1:
+            raise ValueError(f"transfer_recording: {name} must be a mono waveform [L] of at least "
+                             f"{audio.N_FFT // 2 + 1} samples, got shape {tuple(y.shape)}")
+    if not 1 <= num_timesteps <= model.num_timesteps:
+        raise ValueError(f"transfer_recording: num_timesteps {num_timesteps} outside the model's schedule "
+                         f"(1..{model.num_timesteps})")
+    if batch_size < 1:
+        raise ValueError(f"transfer_recording: batch_size must be positive, got {batch_size}")
+    Ln = content.numel()
+    T_total = 1 + Ln // HOP
+    N, _ = longform.window_plan(T_total, frames, overlap)
+
+    x, ref_db = longform.mel_windows(audio.melspectrogram(content, sr=sr, n_mels=n_mels), frames, overlap, max_db)
+    Ps = audio.melspectrogram(style, sr=sr, n_mels=n_mels)
+    xs, _ = longform.mel_windows(Ps, frames, 0, max_db)
+    Ns = max(1, Ps.shape[-1] // frames)       # the full windows; a style shorter than one keeps its padded window
+    xs = xs[:Ns]
+
+    latent = model.unet.enc1.weight.shape[1]
+    noise = torch.randn((N, latent, n_mels // 8, frames // 8), generator=torch.Generator().manual_seed(int(seed)))
+    noise = noise.to(content.device)
+    pair = torch.arange(N, device=content.device) % Ns
+    out = []
+    with torch.no_grad():
+        for b0 in range(0, N, batch_size):
+            b1 = min(b0 + batch_size, N)
+            decoded, _ = model.content_style_transfer_wrapper(x[b0:b1], xs[pair[b0:b1]], num_timesteps=num_timesteps,
+                                                              eta=eta, noise=noise[b0:b1])
+            out.append(decoded)
+    windows_out = torch.cat(out)
+    mel_power = longform.stitch_windows(windows_out, ref_db, overlap, T_total, max_db)
+    y = audio.mel_to_audio(mel_power, sr=sr, n_iter=n_iter, nnls_iters=nnls_iters, seed=seed, length=Ln)
+    return SimpleNamespace(audio=y, mel_power=mel_power, windows_out=windows_out, ref_db=ref_db, N=N)
+
+
+def load_model(checkpoint=None, device="cuda"):
+    """An eval-mode LDM on `device`; `checkpoint` is a full ldm.pth state dict, loaded by component prefix the way
+    LDM.__init__ does (None: freshly initialised weights)."""
+    from .config import config
+    from .model import LDM
+    model = LDM(config["latent_dim_encoder"], pretrained_path="")
+    if checkpoint:
+        sd = torch.load(checkpoint, map_location="cpu", weights_only=True)
+        for prefix, mod in (("encoder.", model.encoder), ("decoder.", model.decoder), ("unet.", model.unet),
+                            ("style_encoder.", model.style_encoder), ("noise_scheduler.", model.noise_scheduler)):
+            mod.load_state_dict({k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)})
+    return model.to(device).eval()
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog="python -m models.transfer", description=__doc__.split("\n\n")[0])
+    p.add_argument("--content", required=True, help="the recording to transfer (.wav, PCM16 or float32, any rate)")
+    p.add_argument("--style", required=True, help="the recording whose style is applied (.wav)")
+    p.add_argument("--out", required=True, help="the .wav to write (mono PCM16 at 22050 Hz)")
+    p.add_argument("--checkpoint", default=None, help="a full ldm.pth state dict (default: untrained weights)")
+    p.add_argument("--frames", type=int, default=512, help="mel frames per window")
+    p.add_argument("--overlap", type=int, default=64, help="mel frames two neighbouring windows share")
+    p.add_argument("--steps", type=int, default=100, help="diffusion steps per window")
+    p.add_argument("--eta", type=float, default=0.0)
+    p.add_argument("--batch", type=int, default=8, help="windows per model call")
+    p.add_argument("--seed", type=int, default=0)
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from data.audio_processor import AudioPreprocessor
+    ap = AudioPreprocessor()
+    content, sr = ap.load_audio_native(args.content)
+    style, _ = ap.load_audio_native(args.style)
+    content, style = ap.trim_silence(content), ap.trim_silence(style)
+    model = load_model(args.checkpoint)
+    res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
+                             num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed)
+    ap.save_wav(args.out, res.audio, sr)
+    print(f"{args.out}: {res.audio.numel() / sr:.1f} s, {res.N} windows of {args.frames} frames "
+          f"({math.ceil(res.N / args.batch)} model calls)")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
