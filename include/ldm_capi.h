@@ -274,6 +274,14 @@ int ldm_sched_backward(int32_t kind, const float* grad, const float* coef_table,
  * sequence for identical inputs (no FMA contraction). */
 int ldm_ddim_step(float* x, const float* eps, const float* coef, float eta, float* x0_log, float* eps_log,
                   int64_t n, void* stream);
+/* One step of the multistep solver (DPM-Solver++ in its data-prediction form) on n elements, x in place:
+ *   x0 = (x - sigma_t eps) / alpha_t;  x <- (c_x x + c_0 x0) + c_1 x0_prev,
+ * fp32 with one rounding per operation.  coef: one row [8] {alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0} of
+ * ForwardDiffusion.multistep_coefs (device).  x0_prev: the previous step's x0, or NULL for a first-order step
+ * (the term and its load are skipped).  x0_log (required, not x0_prev) receives x0; eps_log (or NULL) a copy
+ * of eps. */
+int ldm_msolver_step(float* x, const float* eps, const float* coef, const float* x0_prev, float* x0_log,
+                     float* eps_log, int64_t n, void* stream);
 
 /* ---- loss reductions (loss.py): kind 0 = mean((a-b)^2) (diffusion_loss :48-49, nn.MSELoss :35),
  * kind 1 = mean(0.5*(a^2-1-log(a^2+1e-8))) (kl_regularization_loss :31-32, b unused).
@@ -361,6 +369,13 @@ int64_t ldm_ddim_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weight
 int ldm_ddim_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
                     const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta,
                     float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
+/* The same loop with the multistep solver's update (ldm_msolver_step) fused into dec1: coef_table [nsteps, 8]
+ * (ForwardDiffusion.multistep_coefs), no eta.  Same time-MLP and K/V hoisting, fold and step-kernel selection,
+ * workspace (ldm_ddim_workspace_floats) and log_step_stride meaning.  x0_logs is required: it is the solver's
+ * history (step i reads the slot of step i-1; step 0 reads none).  eps_logs stays optional. */
+int ldm_msolver_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                       const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps,
+                       float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
 
 /* ---- data formats either side of the path (dataio.hip) ---------------------------
  * ldm_mel_quantize: the reference's 8-bit mel PNG pixels, uint8(clip((db + max_db) * 255/max_db, 0, 255)
@@ -486,6 +501,11 @@ int ldm_step_conv_ws(int32_t layer, int32_t B, int32_t H, int32_t W, const float
 int ldm_step_dec1_ddim(int32_t B, int32_t H, int32_t W, const float* d2, const float* packed, const float* bias,
                        const float* coef, float eta, float* xs, float* x0_log, float* eps_log, int32_t dtype,
                        void* stream);
+/* Its twin with the multistep update (ldm_msolver_step's arithmetic, fp32 whatever dtype is): coef [8]; x0_prev
+ * (NCHW like the logs, or NULL) is read with the stride x0_log is written with; x0_log is required. */
+int ldm_step_dec1_msolver(int32_t B, int32_t H, int32_t W, const float* d2, const float* packed, const float* bias,
+                          const float* coef, float* xs, const float* x0_prev, float* x0_log, float* eps_log,
+                          int32_t dtype, void* stream);
 /* Which reverse-loop layers run uconv.hip's K-split form (bit l = layer l; LDM_UCONV_KS, default enc4 +
  * bottleneck + dec4); every other layer runs the single-block form. */
 int ldm_step_layer_forms(int32_t* ks_layers);

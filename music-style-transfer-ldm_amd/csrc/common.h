@@ -188,6 +188,10 @@ struct EpiArgs {
     int32_t round_out;
     // 16-bit storage (LDM_DT_X16 / LDM_DT_Y16, in the lowp type): the input x, and the output y with act_out
     int32_t x16, y16;
+    // fused multistep solver update (msolver_update) instead of the DDIM one: ddim_coef stays NULL, ddim_x /
+    // ddim_x0_log (required: the solver's history) / ddim_eps_log are the sampler state and logs as above
+    const float* ms_coef;      // [8] {alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0} or NULL
+    const float* ms_x0_prev;   // the previous step's x0 log (laid out like ddim_x0_log), or NULL: first-order step
 };
 
 // conv.hip: implicit-GEMM conv with the full internal epilogue (incl. the fused DDIM update); y may be
@@ -230,6 +234,8 @@ struct StepConv {
     float* xs;            // dec1: sampler state (NHWC), updated in place
     float* x0_log;        // dec1: NCHW logs (or NULL)
     float* eps_log;
+    int msolver;          // dec1: the multistep update (coef = an 8-float row, x0_log required) instead of DDIM's
+    const float* x0_prev; // dec1, msolver: the previous step's x0 log (NCHW), or NULL for a first-order step
     int dtype;            // operand precision: LDM_DT_F32 / LDM_DT_F16 / LDM_DT_BF16 (uconv.hip)
     float* ws;            // split-K workspace (step_ws_floats; zero-filled once) for the K-split layers
 };
@@ -262,6 +268,25 @@ __device__ __forceinline__ float ddim_update(float xv, float e, const float* coe
     const float nc = eta * (dxn - dxt);   // noise_contribution
     const float t1 = san * x0;
     return (t1 + dxn) + nc;
+}
+
+// One step of the multistep solver (DPM-Solver++ in its data-prediction form) for one element, with the same
+// rounding discipline.  coef = {alpha_t, sigma_t, c_x, c_0, c_1, ...} (ForwardDiffusion.multistep_coefs);
+// x0_prev: the previous step's x0 at this element, read only when has_prev (uniform over a launch).
+__device__ __forceinline__ float msolver_update(float xv, float e, const float* coef, bool has_prev, float x0_prev,
+                                                float& x0) {
+#pragma clang fp contract(off)
+    const float at = coef[0], st = coef[1], cx = coef[2], c0 = coef[3];
+    const float dxt = st * e;
+    x0 = (xv - dxt) / at;                 // the same data prediction as ddim_update
+    const float t0 = cx * xv;
+    const float t1 = c0 * x0;
+    float xn = t0 + t1;
+    if (has_prev) {
+        const float t2 = coef[4] * x0_prev;
+        xn = xn + t2;
+    }
+    return xn;
 }
 
 // v rounded to a 16-bit type (LDM_DT_F16 / LDM_DT_BF16, round to nearest even), or unchanged (0)

@@ -1639,9 +1639,11 @@ namespace ldm {
 
 int conv_forward_ex(const ldm_conv_desc& d, const ldm_conv_plan& p, const float* x, const float* w, const EpiArgs& ep,
                     float* y, float* ws, hipStream_t st) {
-    LDM_REQUIRE(x && w && (y || ep.ddim_coef), "conv forward: null argument");
+    LDM_REQUIRE(x && w && (y || ep.ddim_coef || ep.ms_coef), "conv forward: null argument");
     LDM_REQUIRE(p.ws_floats == 0 || ws, "conv forward: this plan splits K across blocks and needs a workspace");
     LDM_REQUIRE(!ep.ddim_coef || ep.ddim_x, "conv forward: fused DDIM update needs x");
+    LDM_REQUIRE(!ep.ms_coef || (ep.ddim_x && ep.ddim_x0_log && !ep.ddim_coef && ep.ms_x0_prev != ep.ddim_x0_log),
+                "conv forward: fused multistep update needs x and its x0 log, and excludes the DDIM one");
     if (p.kind == 3) return tconv_forward(d, p, x, w, ep, y, st);
     if (p.kind == 4) return sconv_forward(d, p, x, w, ep, y, st);
     ConvArgs a;
@@ -1660,7 +1662,7 @@ int conv_forward_ex(const ldm_conv_desc& d, const ldm_conv_plan& p, const float*
         a.fd_dwo = FastDiv::make(d.Wout);
         a.fd_dho = FastDiv::make(d.Hout);
         a.fd_dco = FastDiv::make(d.Cout);
-        const bool simple_epi = !ep.pos_bias && !ep.bcast && !ep.skip && !ep.ddim_coef && y;
+        const bool simple_epi = !ep.pos_bias && !ep.bcast && !ep.skip && !ep.ddim_coef && !ep.ms_coef && y;
         if (simple_epi && d.Cin == 1 && !d.transposed && d.Cout <= 64 && d.kh == d.kw &&
             ((d.stride == 2 && (d.kh == 3 || d.kh == 4)) || (d.stride == 1 && d.kh == 3 && cin1_s1_on())) && d.Wout % 4 == 0 && a.pt.dy[0][0] == -d.pad && a.pt.dx[0][0] == -d.pad &&
             ((uintptr_t)y & 15) == 0 && (!ep.act_out || ((uintptr_t)ep.act_out & 15) == 0)) {

@@ -1,6 +1,6 @@
 // ConvArgs and the conv epilogue (conv.hip's implicit-GEMM kernels and sconv.hip's small-plane kernel share them):
 // the reference's op order conv + bias -> BN(eval) -> act -> + bcast -> + skip (model.py:16-25, :205-229), with
-// autocast output rounding and the fused DDIM update.
+// autocast output rounding and the fused DDIM / multistep-solver update.
 #pragma once
 #include "common.h"
 
@@ -61,7 +61,7 @@ __device__ __forceinline__ EpiPre epi_prefetch(const ConvArgs& a, int m, int b, 
     p.bias = e.pos_bias ? e.pos_bias[m * a.Hout * a.Wout + pix] : (e.bias ? e.bias[m] : 0.f);
     p.bcast = e.bcast ? e.bcast[(size_t)b * a.Cout + m] : 0.f;
     p.skip = e.skip ? e.skip[oidx] : 0.f;
-    p.x = e.ddim_coef ? e.ddim_x[oidx] : 0.f;
+    p.x = (e.ddim_coef || e.ms_coef) ? e.ddim_x[oidx] : 0.f;
     return p;
 }
 
@@ -85,7 +85,7 @@ __device__ __forceinline__ EpiSrc epi_sources(const ConvArgs& a, bool live) {
                         : opt_rsrc(e.bias, live ? a.Cout * 4 : 0);
     s.bcast = opt_rsrc(e.bcast, live ? a.B * a.Cout * 4 : 0);
     s.skip = opt_rsrc(e.skip, ybytes);
-    s.x = opt_rsrc(e.ddim_coef ? e.ddim_x : nullptr, ybytes);
+    s.x = opt_rsrc((e.ddim_coef || e.ms_coef) ? e.ddim_x : nullptr, ybytes);
     return s;
 }
 
@@ -119,6 +119,15 @@ __device__ __forceinline__ void epi_finish(const ConvArgs& a, int m, size_t oidx
     if (e.act_out) e.act_out[oidx] = v;
     if (e.bcast) v = round16(v + p.bcast, ro);
     if (e.skip) v = round16(v + p.skip, ro);
+    if (e.ms_coef) {   // the multistep solver's update (uniform branches; its history is read here, not prefetched)
+        const bool hp = e.ms_x0_prev != nullptr;
+        float x0;
+        e.ddim_x[oidx] = msolver_update(p.x, v, e.ms_coef, hp, hp ? e.ms_x0_prev[oidx] : 0.f, x0);
+        e.ddim_x0_log[oidx] = x0;
+        if (e.ddim_eps_log) e.ddim_eps_log[oidx] = v;
+        if (a.y) a.y[oidx] = v;
+        return;
+    }
     if (e.ddim_coef) {
         float x0;
         e.ddim_x[oidx] = ddim_update(p.x, v, e.ddim_coef, e.ddim_eta, x0);

@@ -606,6 +606,21 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, c
     if (eps_log) eps_log[i] = e;
 }
 
+// x0_prev == NULL: a first-order step.  x0_log may alias nothing else; x0_prev is another step's log.
+__global__ __launch_bounds__(256) void msolver_step_kernel(float* __restrict__ x, const float* __restrict__ eps,
+                                                           const float* __restrict__ coef,
+                                                           const float* __restrict__ x0_prev, float* __restrict__ x0_log,
+                                                           float* __restrict__ eps_log, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float e = eps[i];
+    const bool hp = x0_prev != nullptr;
+    float x0;
+    x[i] = msolver_update(x[i], e, coef, hp, hp ? x0_prev[i] : 0.f, x0);
+    x0_log[i] = x0;
+    if (eps_log) eps_log[i] = e;
+}
+
 // (train-mode BatchNorm2d lives in reduce.hip)
 
 __global__ __launch_bounds__(256) void activation_kernel(const float* x, float* y, int64_t n, int act) {
@@ -880,6 +895,16 @@ extern "C" int ldm_ddim_step(float* x, const float* eps, const float* coef, floa
     hipLaunchKernelGGL(ddim_step_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, eps, coef, eta,
                        x0_log, eps_log, n);
     LDM_CHECK_LAUNCH("ddim_step_kernel");
+    return 0;
+}
+
+extern "C" int ldm_msolver_step(float* x, const float* eps, const float* coef, const float* x0_prev, float* x0_log,
+                                float* eps_log, int64_t n, void* stream) {
+    LDM_REQUIRE(x && eps && coef && x0_log && n > 0, "msolver_step: bad argument");
+    LDM_REQUIRE(x0_prev != x0_log, "msolver_step: x0_prev must not be the x0 output");
+    hipLaunchKernelGGL(msolver_step_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, eps, coef,
+                       x0_prev, x0_log, eps_log, n);
+    LDM_CHECK_LAUNCH("msolver_step_kernel");
     return 0;
 }
 

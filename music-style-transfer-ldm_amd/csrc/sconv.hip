@@ -319,7 +319,7 @@ int sconv_forward(const ldm_conv_desc& d, const ldm_conv_plan& p, const float* x
     LDM_REQUIRE(p.kind == 4 && (p.tn == LDM_DT_F16 || p.tn == LDM_DT_BF16), "sconv: not a kind-4 plan");
     LDM_REQUIRE(ep.lowp == p.tn, "sconv: the plan's operand precision differs from the call's");
     LDM_REQUIRE(!ep.x16 && !ep.y16, "sconv: fp32 maps only");
-    LDM_REQUIRE(!ep.ddim_coef && !ep.pos_bias && y, "sconv: no fused update / position bias");
+    LDM_REQUIRE(!ep.ddim_coef && !ep.ms_coef && !ep.pos_bias && y, "sconv: no fused update / position bias");
     sc::SArgs s;
     int nph, nw;
     size_t lds;

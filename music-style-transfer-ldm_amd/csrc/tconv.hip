@@ -998,7 +998,7 @@ int tconv_forward(const ldm_conv_desc& d, const ldm_conv_plan& p, const float* x
     LDM_REQUIRE(p.kind == 3 && (p.tm == 1 || p.tm == 2) && (p.tn == LDM_DT_F16 || p.tn == LDM_DT_BF16),
                 "tconv: not a kind-3 plan");
     LDM_REQUIRE(ep.lowp == p.tn, "tconv: the plan's operand precision differs from the call's");
-    LDM_REQUIRE(!ep.pos_bias && !ep.bcast && !ep.skip && !ep.ddim_coef && y,
+    LDM_REQUIRE(!ep.pos_bias && !ep.bcast && !ep.skip && !ep.ddim_coef && !ep.ms_coef && y,
                 "tconv: only bias / eval-BN / activation epilogues");
     ldm_conv_plan chk;
     LDM_REQUIRE(tconv_plan(d, p.tn, chk) && chk.tm == p.tm && chk.packed_floats == p.packed_floats,

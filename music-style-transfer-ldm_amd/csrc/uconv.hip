@@ -41,7 +41,9 @@
 namespace ldm {
 namespace uc {
 
-enum : int { EPI_RELU = 1, EPI_BCAST = 2, EPI_SKIP = 4, EPI_POSB = 8, EPI_DDIM = 16, EPI_PLANE = 32, EPI_WINDOW = 64 };
+enum : int { EPI_RELU = 1, EPI_BCAST = 2, EPI_SKIP = 4, EPI_POSB = 8, EPI_DDIM = 16, EPI_PLANE = 32, EPI_WINDOW = 64, EPI_MSOLVER = 128 };
+// EPI_MSOLVER: dec1's epilogue is the multistep solver's update (msolver_update) in place of EPI_DDIM's; its
+// instances are separate ones, so the EPI_DDIM instances are compiled exactly as without it.
 // EPI_PLANE (a geometry flag carried with the epilogue bits): the layer's plane is 2 x 8 (the bottleneck at the
 // canonical 16 x 64 latent), so the 16 columns of a lane group are one sample's whole plane and every tap of a
 // stride-1 3x3 conv reads a position some lane of the group already holds.  Each channel chunk's activation
@@ -74,6 +76,8 @@ struct UArgs {
     FastDiv fd_hw, fd_w, fd_mt, fd_nt, fd_tiles;
     float* slab;          // KS > 1: partial tiles [tile][KS][NFR][64] float4 (write-through)
     int32_t* cnt;         // KS > 1: arrival counter per tile (zero between launches)
+    const float* x0_prev; // EPI_MSOLVER: the previous step's pred_x0 log (NCHW like x0_log), or NULL (first-order step);
+                          // coef is then the [8] row {alpha_t, sigma_t, c_x, c_0, c_1, ...} and x0_log is required
 };
 
 // (ky, kx) of tap t and the conv input offset / the transposed conv's output parity
@@ -348,7 +352,7 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
         o.ok = f < NFR && colsel(cval, ni) != 0;
         return o;
     };
-    floatx4 pre_b[NMY], pre_c[NMY], pre_s[NMY];
+    floatx4 pre_b[NMY], pre_c[NMY], pre_s[NMY], pre_h[NMY];
     auto epi_prefetch = [&]() {
         static_for<0, NMY>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
@@ -359,6 +363,15 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
             if constexpr ((EPI & EPI_BCAST) != 0) pre_c[k] = *reinterpret_cast<const floatx4*>(a.bcast + (size_t)o.b * COUT + o.m);
             if constexpr ((EPI & EPI_SKIP) != 0) pre_s[k] = *reinterpret_cast<const floatx4*>(a.skip + (size_t)o.pix * COUT + o.m);
             if constexpr ((EPI & EPI_DDIM) != 0) pre_s[k] = *reinterpret_cast<const floatx4*>(a.xs + (size_t)o.pix * COUT + o.m);
+            if constexpr ((EPI & EPI_MSOLVER) != 0) {
+                pre_s[k] = *reinterpret_cast<const floatx4*>(a.xs + (size_t)o.pix * COUT + o.m);
+                if (a.x0_prev) {   // uniform: the solver's history, read with the stride its log was written with
+                    const size_t hw = (size_t)a.Hout * a.Wout;
+                    const size_t lbase = ((size_t)o.b * COUT + o.m) * hw + (size_t)o.oy * a.Wout + o.ox;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pre_h[k][r] = a.x0_prev[lbase + r * hw];
+                }
+            }
         });
     };
 
@@ -688,7 +701,22 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = round16(o[r] + pre_s[k][r], DT);
         }
-        if constexpr ((EPI & EPI_DDIM) != 0) {
+        if constexpr ((EPI & EPI_MSOLVER) != 0) {
+            // noise_pred = o; the multistep update (msolver_update, one rounding per op), fp32 whatever DT is
+            const floatx4 xv = pre_s[k];
+            floatx4 xn;
+            const bool hp = a.x0_prev != nullptr;
+            const size_t hw = (size_t)a.Hout * a.Wout;
+            const size_t lbase = ((size_t)ot.b * COUT + ot.m) * hw + (size_t)ot.oy * a.Wout + ot.ox;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float x0;
+                xn[r] = msolver_update(xv[r], o[r], a.coef, hp, hp ? pre_h[k][r] : 0.f, x0);
+                a.x0_log[lbase + r * hw] = x0;
+                if (a.eps_log) a.eps_log[lbase + r * hw] = o[r];
+            }
+            *reinterpret_cast<floatx4*>(a.xs + (size_t)ot.pix * COUT + ot.m) = xn;
+        } else if constexpr ((EPI & EPI_DDIM) != 0) {
             // noise_pred = o; the reverse update of model.py:442-458 (ddim_update, one rounding per op)
             const floatx4 xv = pre_s[k];
             floatx4 xn;
@@ -1083,6 +1111,7 @@ static int make_args(int layer, int B, int H, int W, const StepConv& s, int ksv,
     a.x0_log = s.x0_log;
     a.eps_log = s.eps_log;
     a.eta = s.eta;
+    a.x0_prev = s.x0_prev;
     a.B = B;
     a.Hin = Hin;
     a.Win = Win;
@@ -1132,6 +1161,7 @@ static int make_args(int layer, int B, int H, int W, const StepConv& s, int ksv,
     LDM_REQUIRE((int64_t)B * Hin * Win * g.cin * 4 < 0x7ff00000LL && (int64_t)B * a.Hout * a.Wout * g.cout * 4 < 0x7ff00000LL,
                 "step conv: tensor too large for 32-bit buffer offsets");
     LDM_REQUIRE(s.x && s.w && s.bias, "step conv: null operand");
+    LDM_REQUIRE(!s.msolver || (layer == 8 && s.x0_log), "step conv: the multistep update is dec1's and needs its x0 log");
     return 0;
 }
 }  // namespace uc
@@ -1155,6 +1185,7 @@ int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st)
             case 7: LDM_REQUIRE(s.y && s.skip && win && a.Wq % 32 == 0, "dec2 (variant 3): y, skip, 32-column rows");
                 return launch<2, 128, 64, 1, 2, 1, 8, 9, 9, EPI_RELU | EPI_SKIP | EPI_WINDOW, 1>(a, s.dtype, st);
             case 8: LDM_REQUIRE(s.xs && s.coef && win && a.Wq % 64 == 0, "dec1 (variant 3): sampler state, 64-column rows");
+                if (s.msolver) return launch<0, 64, 32, 1, 2, 2, 4, 9, 9, EPI_MSOLVER | EPI_WINDOW, 1>(a, s.dtype, st);
                 return launch<0, 64, 32, 1, 2, 2, 4, 9, 9, EPI_DDIM | EPI_WINDOW, 1>(a, s.dtype, st);
             case 3: LDM_REQUIRE(s.y && a.Hin == 4 && a.Win == 16 && plane_taps(), "enc4 (variant 3): y, 4 x 16 input plane");
                 return launch<1, 256, 512, 1, 1, 1, 16, 9, 9, EPI_RELU | EPI_POSB | EPI_PLANE, 1>(a, s.dtype, st);
@@ -1238,6 +1269,15 @@ int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st)
                 return launch<2, 128, 64, 1, 2, 1, 4, 18, 18, EPI_RELU | EPI_SKIP | EPI_WINDOW>(a, s.dtype, st);
             return launch<2, 128, 64, 1, 2, 1, 4, 18, 18, EPI_RELU | EPI_SKIP>(a, s.dtype, st);
         default: LDM_REQUIRE(s.xs && s.coef, "dec1: sampler state, coefficients");
+            if (s.msolver) {   // the same four geometries with the multistep epilogue
+                if (dec1_thin(W)) {
+                    if (window_taps()) return launch<0, 64, 32, 1, 2, 2, 2, 18, 18, EPI_MSOLVER | EPI_WINDOW>(a, s.dtype, st);
+                    return launch<0, 64, 32, 1, 2, 2, 2, 18, 18, EPI_MSOLVER>(a, s.dtype, st);
+                }
+                if (window_taps() && a.Wq % 32 == 0)
+                    return launch<0, 64, 32, 2, 2, 1, 4, 9, 9, EPI_MSOLVER | EPI_WINDOW>(a, s.dtype, st);
+                return launch<0, 64, 32, 2, 2, 1, 4, 9, 9, EPI_MSOLVER>(a, s.dtype, st);
+            }
             if (dec1_thin(W)) {
                 if (window_taps()) return launch<0, 64, 32, 1, 2, 2, 2, 18, 18, EPI_DDIM | EPI_WINDOW>(a, s.dtype, st);
                 return launch<0, 64, 32, 1, 2, 2, 2, 18, 18, EPI_DDIM>(a, s.dtype, st);
@@ -1339,6 +1379,25 @@ extern "C" int ldm_step_dec1_ddim(int32_t B, int32_t H, int32_t W, const float* 
     s.coef = coef;
     s.eta = eta;
     s.xs = xs;
+    s.x0_log = x0_log;
+    s.eps_log = eps_log;
+    return step_conv(8, B, H, W, s, (hipStream_t)stream);
+}
+
+extern "C" int ldm_step_dec1_msolver(int32_t B, int32_t H, int32_t W, const float* d2, const float* packed,
+                                     const float* bias, const float* coef, float* xs, const float* x0_prev, float* x0_log,
+                                     float* eps_log, int32_t dtype, void* stream) {
+    LDM_REQUIRE(d2 && packed && bias && coef && xs && x0_log, "ldm_step_dec1_msolver: null argument");
+    LDM_REQUIRE(x0_prev != x0_log, "ldm_step_dec1_msolver: x0_prev must not be the x0 output");
+    StepConv s{};
+    s.dtype = dtype;
+    s.x = d2;
+    s.w = packed;
+    s.bias = bias;
+    s.coef = coef;
+    s.xs = xs;
+    s.msolver = 1;
+    s.x0_prev = x0_prev;
     s.x0_log = x0_log;
     s.eps_log = eps_log;
     return step_conv(8, B, H, W, s, (hipStream_t)stream);

@@ -173,6 +173,8 @@ struct DdimFuse {
     float* x;
     float* x0_log;
     float* eps_log;
+    bool msolver;            // the multistep solver's update instead: coef is an 8-float row, eta unused, x0_log required
+    const float* x0_prev;    // msolver: the previous step's x0 log or NULL (first-order step)
 };
 
 static int conv_call(const ldm_unet_shape& s, float* convws, int layer, const ldm_conv_plan& plan, const float* x, const float* w,
@@ -188,7 +190,8 @@ static int conv_call(const ldm_unet_shape& s, float* convws, int layer, const ld
     ep.bcast = bcast;
     ep.skip = skip;
     if (fuse) {
-        ep.ddim_coef = fuse->coef;
+        if (fuse->msolver) ep.ms_coef = fuse->coef, ep.ms_x0_prev = fuse->x0_prev;
+        else ep.ddim_coef = fuse->coef;
         ep.ddim_eta = fuse->eta;
         ep.ddim_x = fuse->x;
         ep.ddim_x0_log = fuse->x0_log;
@@ -307,6 +310,8 @@ static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w,
     c[8].xs = ws.xs;
     c[8].x0_log = fuse.x0_log;
     c[8].eps_log = fuse.eps_log;
+    c[8].msolver = fuse.msolver;
+    c[8].x0_prev = fuse.x0_prev;
     auto run = [&](int l0, int l1) -> int {   // layers [l0, l1]
         for (int l = l0; l <= l1; ++l) LDM_TRY(step_conv(l, s.B, s.H, s.W, c[l], st));
         return 0;
@@ -367,19 +372,18 @@ extern "C" int ldm_unet_forward(const ldm_unet_shape* s, const ldm_unet_weights*
     return unet_forward(*s, *w, z, t, t_is_float, s5, s6, out, ws, (hipStream_t)stream);
 }
 
-extern "C" int ldm_ddim_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                               const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps,
-                               float eta, float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
-                               void* stream) {
-    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace, "ddim_sample: null argument");
-    LDM_REQUIRE(nsteps >= 0, "ddim_sample: negative step count");
-    if (nsteps == 0) return 0;
+// The reverse loop of both samplers.  msolver: coef_table is [nsteps, 8] (multistep rows) and every step i > 0 reads
+// step i-1's slot of x0_logs as its history (a first-order row there carries c_1 = 0); step 0 has none to read.
+static int sample_loop(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
+                       const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta, float* x0_logs,
+                       float* eps_logs, int64_t log_step_stride, float* workspace, void* stream, bool msolver) {
     UNetWs ws = carve(*s, w, workspace);
     float* temb_all = workspace + ws.total;   // [nsteps*B, 128] (ldm_ddim_workspace_floats)
     const int64_t dense = (int64_t)s->B * s->C * s->H * s->W;
     LDM_REQUIRE(log_step_stride == 0 || log_step_stride >= dense, "ddim_sample: log stride smaller than a step");
     const int64_t n = log_step_stride ? log_step_stride : dense;
     hipStream_t st = (hipStream_t)stream;
+    const size_t cw = msolver ? 8 : 4;   // floats per coefficient row
     // The time MLP depends only on t: all nsteps*B embeddings in one launch before the loop (the same
     // evaluations the reference makes one step at a time, model.py:203).
     LDM_TRY(ldm_time_mlp_forward(t_table, 0, nsteps * s->B, 128, w->t_freqs, w->t_w1, w->t_b1, w->t_w2, w->t_b2,
@@ -402,15 +406,17 @@ extern "C" int ldm_ddim_sample(const ldm_unet_shape* s, const ldm_unet_weights* 
             if (use_bneck_fold(*s, w)) LDM_TRY(bneck_fold_values(w->step_bneck_w, ws.kv1, ws.ubn, s->B, st));
             LDM_TRY(step_layout(x, ws.xs, s->B, s->C, HW, true, st));
             for (int i = 0; i < nsteps; ++i) {
-                DdimFuse fuse{coef_table + 4 * (size_t)i, eta, ws.xs, x0_logs ? x0_logs + (size_t)i * n : nullptr,
-                              eps_logs ? eps_logs + (size_t)i * n : nullptr};
+                DdimFuse fuse{coef_table + cw * (size_t)i, eta, ws.xs, x0_logs ? x0_logs + (size_t)i * n : nullptr,
+                              eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
+                              msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
                 LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse));
             }
             return step_layout(ws.xs, x, s->B, s->C, HW, false, st);
         }
         for (int i = 0; i < nsteps; ++i) {
-            DdimFuse fuse{coef_table + 4 * (size_t)i, eta, x, x0_logs ? x0_logs + (size_t)i * n : nullptr,
-                          eps_logs ? eps_logs + (size_t)i * n : nullptr};
+            DdimFuse fuse{coef_table + cw * (size_t)i, eta, x, x0_logs ? x0_logs + (size_t)i * n : nullptr,
+                          eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
+                          msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
             LDM_TRY(unet_forward_folded(*s, *w, x, ws, st, temb_all + (size_t)i * s->B * 128, &fuse));
         }
         return 0;
@@ -419,12 +425,37 @@ extern "C" int ldm_ddim_sample(const ldm_unet_shape* s, const ldm_unet_weights* 
         // noise_pred = unet(x, t, style_embedding)                                (model.py:439)
         // and, fused into dec1's epilogue, the x0 / direction / eta update and the two log clones
         // (model.py:442-463) — bitwise the same fp32 op sequence as ldm_ddim_step.
-        DdimFuse fuse{coef_table + 4 * (size_t)i, eta, x, x0_logs ? x0_logs + (size_t)i * n : nullptr,
-                      eps_logs ? eps_logs + (size_t)i * n : nullptr};
+        DdimFuse fuse{coef_table + cw * (size_t)i, eta, x, x0_logs ? x0_logs + (size_t)i * n : nullptr,
+                      eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
+                      msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
         LDM_TRY(unet_forward(*s, *w, x, t_table + (size_t)i * s->B, 0, s5, s6, nullptr, ws, st,
                              temb_all + (size_t)i * s->B * 128, &fuse, /*kv_ready=*/true));
     }
     return 0;
+}
+
+extern "C" int ldm_ddim_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                               const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps,
+                               float eta, float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
+                               void* stream) {
+    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace, "ddim_sample: null argument");
+    LDM_REQUIRE(nsteps >= 0, "ddim_sample: negative step count");
+    if (nsteps == 0) return 0;
+    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, eta, x0_logs, eps_logs, log_step_stride, workspace,
+                       stream, false);
+}
+
+// The multistep (DPM-Solver++(2M) / first-order) twin: same hoisting, fold and step selection, workspace
+// (ldm_ddim_workspace_floats) and log_step_stride meaning; x0_logs is the solver's history and required.
+extern "C" int ldm_msolver_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                                  const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps,
+                                  float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
+                                  void* stream) {
+    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace && x0_logs, "msolver_sample: null argument");
+    LDM_REQUIRE(nsteps >= 0, "msolver_sample: negative step count");
+    if (nsteps == 0) return 0;
+    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs, log_step_stride, workspace,
+                       stream, true);
 }
 
 extern "C" int64_t ldm_ddim_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps) {

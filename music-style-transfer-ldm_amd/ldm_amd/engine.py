@@ -258,6 +258,29 @@ class UNetEngine:
                t_table.data_ptr(), coef_table.data_ptr(), n, float(eta), ops._p(x0_logs), ops._p(eps_logs),
                int(log_stride), ws.data_ptr(), ops.stream_handle())
 
+    def _msolver_call(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs, log_stride, slot):
+        B, C, H, W = x.shape
+        shape = self.shape(B, C, H, W)
+        w = self.weights(shape)
+        n = t_table.shape[0]
+        ws = self.workspace(shape, x.device, n, slot)
+        L.call("ldm_msolver_sample", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(),
+               t_table.data_ptr(), coef_table.data_ptr(), n, x0_logs.data_ptr(), ops._p(eps_logs), int(log_stride),
+               ws.data_ptr(), ops.stream_handle())
+
+    def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None):
+        """ddim_loop's twin for the multistep solver (DPM-Solver++(2M) or its first-order form): coef_table
+        [n,8] from ForwardDiffusion.multistep_coefs (device), no eta.  x0_logs [n,B,C,H,W] is required: step i
+        reads step i-1's slot as its history.  Same sub-batch chains as ddim_loop."""
+        if x0_logs is None:
+            raise ValueError("msolver_loop: x0_logs is required (it is the solver's history)")
+        if coef_table.dim() != 2 or coef_table.shape[1] != 8 or coef_table.shape[0] != t_table.shape[0]:
+            raise ValueError(f"msolver_loop: coef_table must be [n,8] for n = {t_table.shape[0]} steps, "
+                             f"got {tuple(coef_table.shape)}")
+        return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
+                          lambda xs, a5, a6, t, x0l, epl, stride, slot:
+                          self._msolver_call(xs, a5, a6, t, coef_table, x0l, epl, stride, slot))
+
     def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None):
         """In-place reverse loop on x ([B,C,H,W] contiguous fp32).  t_table [n,B] int64, coef [n,4] (device).
 
@@ -266,11 +289,18 @@ class UNetEngine:
         The path is per-sample, so the result is the same up to fp32 summation order (a sub-batch
         size may get a conv plan that splits K differently); the chains' launch and memory latencies
         overlap each other's work."""
+        return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
+                          lambda xs, a5, a6, t, x0l, epl, stride, slot:
+                          self._ddim_call(xs, a5, a6, t, coef_table, eta, x0l, epl, stride, slot))
+
+    def _loop(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call):
+        """The whole batch in one C call, or one per sub-batch chain; call(x, s5, s6, t, x0_logs, eps_logs,
+        log_stride, slot) is one sampler's C call."""
         B = x.shape[0]
         if plan is None:
             plan = self.split_plan(t_table, B, split) if split > 1 else None
         if not plan or len(plan) == 1:
-            self._ddim_call(x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, 0, 0)
+            call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0)
             return x
         per_step = x[0].numel() * B
         main = torch.cuda.current_stream(x.device)
@@ -286,9 +316,9 @@ class UNetEngine:
             if not torch.cuda.is_current_stream_capturing():
                 t_sub.record_stream(st)
             with torch.cuda.stream(st):
-                self._ddim_call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, coef_table, eta,
-                                None if x0_logs is None else x0_logs[0, lo:hi],
-                                None if eps_logs is None else eps_logs[0, lo:hi], per_step, k)
+                call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub,
+                     None if x0_logs is None else x0_logs[0, lo:hi],
+                     None if eps_logs is None else eps_logs[0, lo:hi], per_step, k)
         for st in streams:
             main.wait_stream(st)
         return x
@@ -297,7 +327,13 @@ class UNetEngine:
 class GraphedDDIM:
     """A captured reverse loop with static buffers: replay() re-runs all n steps from x_init."""
 
-    def __init__(self, engine, x_init, s5, s6, t_table, coef_table, eta, logs=True, split=1):
+    def __init__(self, engine, x_init, s5, s6, t_table, coef_table, eta, logs=True, split=1, solver="ddim"):
+        """solver="ddim": coef_table [n,4] and eta, the reference's update; solver="msolver": coef_table [n,8]
+        (ForwardDiffusion.multistep_coefs), eta unused and the x0 logs always kept (the solver's history)."""
+        if solver not in ("ddim", "msolver"):
+            raise ValueError(f"GraphedDDIM: unknown solver {solver!r}")
+        self.solver = solver
+        logs = logs or solver == "msolver"
         self.engine = engine
         self.split = split
         dev = x_init.device
@@ -315,16 +351,14 @@ class GraphedDDIM:
         self.plan = engine.split_plan(self.t_table, x_init.shape[0], split) if split > 1 else None
         # warm-up (packs weights, allocates workspaces) outside capture
         self.x.copy_(self.x_init)
-        self.engine.ddim_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.eta, self.x0_logs,
-                              self.eps_logs, plan=self.plan)
+        self._run(plan=self.plan)
         torch.cuda.synchronize()
         if not self.plan:
             self.graphs = [torch.cuda.CUDAGraph()]
             self.streams = None
             with capture(self.graphs[0]):
                 self.x.copy_(self.x_init)
-                self.engine.ddim_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.eta, self.x0_logs,
-                                      self.eps_logs)
+                self._run()
             return
         # One graph per sub-batch chain, each replayed on its own stream: a single graph's parallel
         # branches are executed one after another, separate graphs on separate streams (hardware
@@ -336,10 +370,23 @@ class GraphedDDIM:
             g = torch.cuda.CUDAGraph()
             with capture(g, stream=self.streams[k]):
                 self.x[lo:hi].copy_(self.x_init[lo:hi])
-                engine._ddim_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
-                                  None if self.x0_logs is None else self.x0_logs[0, lo:hi],
-                                  None if self.eps_logs is None else self.eps_logs[0, lo:hi], per_step, k)
+                x0l = None if self.x0_logs is None else self.x0_logs[0, lo:hi]
+                epl = None if self.eps_logs is None else self.eps_logs[0, lo:hi]
+                if solver == "msolver":
+                    engine._msolver_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, x0l, epl,
+                                         per_step, k)
+                else:
+                    engine._ddim_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
+                                      x0l, epl, per_step, k)
             self.graphs.append(g)
+
+    def _run(self, plan=None):
+        if self.solver == "msolver":
+            self.engine.msolver_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.x0_logs, self.eps_logs,
+                                     plan=plan)
+        else:
+            self.engine.ddim_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.eta, self.x0_logs,
+                                  self.eps_logs, plan=plan)
 
     def replay(self):
         if self.streams is None:

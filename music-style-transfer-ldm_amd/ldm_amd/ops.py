@@ -976,6 +976,18 @@ def ddim_step_(x, eps, coef4, eta, x0_log=None, eps_log=None):
     return x
 
 
+def msolver_step_(x, eps, coef8, x0_log, x0_prev=None, eps_log=None):
+    """One multistep-solver step on x in place (ldm_msolver_step): coef8 is one row of
+    ForwardDiffusion.multistep_coefs on the device, x0_prev the previous step's x0 (None: first-order step),
+    x0_log receives this step's x0."""
+    require_device(x, eps, coef8, x0_log, x0_prev, eps_log)
+    if x0_log is None:
+        raise ValueError("msolver_step_: x0_log is required (it is the solver's history)")
+    L.call("ldm_msolver_step", x.data_ptr(), eps.data_ptr(), coef8.data_ptr(), _p(x0_prev), x0_log.data_ptr(),
+           _p(eps_log), x.numel(), stream_handle())
+    return x
+
+
 # ------------------------------------------------------------------------------------------------
 # data formats either side of the path (dataio.hip): 8-bit mel PNG pixels <-> dB, ToTensor
 # ------------------------------------------------------------------------------------------------

@@ -188,6 +188,43 @@ class ForwardDiffusion(nn.Module):
         a_t, a_n = ab[times[:-1]], ab[times[1:]]
         return torch.stack([torch.sqrt(a_t), torch.sqrt(1 - a_t), torch.sqrt(a_n), torch.sqrt(1 - a_n)], 1).contiguous()
 
+    def multistep_coefs(self, times, order=2):
+        """fp32 [n,8] rows {alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0} of the multistep solver (DPM-Solver++ in its
+        data-prediction form) for consecutive `times`, n = len(times) - 1:
+            x0 = (x - sigma_t eps) / alpha_t;   x_next = c_x x + c_0 x0 + c_1 x0_prev.
+        Computed in float64 from alpha_bar_t: alpha = sqrt(ab), sigma = sqrt(1 - ab), lambda = ln(ab / (1 - ab)) / 2,
+        h_i = lambda(t_i+1) - lambda(t_i), phi_i = -expm1(-h_i), c_x = sigma_next / sigma_t.  First order:
+        c_0 = alpha_next phi_i, c_1 = 0.  Second order (2M), r = h_i-1 / h_i: c_0 = alpha_next phi_i (1 + 1/(2r)),
+        c_1 = -alpha_next phi_i / (2r).  Rows 0 and n-1 are always first order (there is no history for the
+        first; the last jumps to index 0, where lambda grows too fast for the extrapolation); order=1 makes
+        every row first order (DDIM with eta = 0)."""
+        if order not in (1, 2):
+            raise ValueError(f"multistep_coefs: order must be 1 or 2, got {order}")
+        ab = self.alpha_bar_t.detach().to("cpu", torch.float64)
+        T = ab.shape[0]
+        times = torch.as_tensor(times).long().cpu()
+        if times.numel() and (int(times.max()) >= T or int(times.min()) < -T):
+            bad = int(times.max()) if int(times.max()) >= T else int(times.min())
+            raise IndexError(f"index {bad} is out of bounds for dimension 0 with size {T}")
+        n = max(int(times.numel()) - 1, 0)
+        out = torch.zeros((n, 8), dtype=torch.float64)
+        if n == 0:
+            return out.float()
+        a = ab[times]
+        alpha, sigma = torch.sqrt(a), torch.sqrt(1 - a)
+        lam = 0.5 * torch.log(a / (1 - a))
+        h = lam[1:] - lam[:-1]
+        phi = -torch.expm1(-h)
+        out[:, 0], out[:, 1] = alpha[:-1], sigma[:-1]
+        out[:, 2] = sigma[1:] / sigma[:-1]
+        out[:, 3] = alpha[1:] * phi
+        if order == 2 and n > 2:
+            r = h[:-1] / h[1:]                      # r_i for rows 1..n-1
+            k = 1.0 / (2.0 * r[:-1])                # rows 1..n-2 are second order
+            out[1:n - 1, 3] = alpha[2:n] * phi[1:n - 1] * (1.0 + k)
+            out[1:n - 1, 4] = -alpha[2:n] * phi[1:n - 1] * k
+        return out.float().contiguous()
+
 
 # ------------------------------------------------------------------------------------------------
 # UNet
@@ -378,13 +415,17 @@ class LDM(nn.Module):
         }
 
     # -------------------------------------------------------------------------------------------
-    def _reverse(self, z_t, style_embedding, times, eta):
-        """The shared body of the two samplers: len(times)-1 UNet + update steps in one C call."""
+    def _reverse(self, z_t, style_embedding, times, eta, order=0):
+        """The shared body of the samplers: len(times)-1 UNet + update steps in one C call.  order 0: the
+        reference's DDIM-style update with eta; 1 / 2: the multistep solver of that order (eta unused)."""
         n = int(times.numel()) - 1
         logs = {"timesteps": [], "pred_x0": [], "noise_pred": []}
         if n <= 0:
             return z_t, logs
-        coefs = self.noise_scheduler.reverse_coefs(times)
+        if order:
+            coefs = self.noise_scheduler.multistep_coefs(times, order=order)
+        else:
+            coefs = self.noise_scheduler.reverse_coefs(times)
         dev = z_t.device
         x = ops.f32c(z_t).clone()
         B = x.shape[0]
@@ -396,12 +437,19 @@ class LDM(nn.Module):
         coefs = coefs.to(dev)
         with torch.no_grad():
             if UNetEngine.supports(x.shape[1]):
-                engine_for(self.unet).ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs)
-            else:   # latent widths the fused engine does not take: per-layer UNet + the DDIM update kernel
+                if order:
+                    engine_for(self.unet).msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs)
+                else:
+                    engine_for(self.unet).ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs)
+            else:   # latent widths the fused engine does not take: per-layer UNet + the update kernel
                 emb = {"s5": s5, "s6": s6}
                 for i in range(n):
                     eps = self.unet(x, t_table[i], emb)
-                    ops.ddim_step_(x, eps, coefs[i].contiguous(), float(eta), x0_logs[i], eps_logs[i])
+                    if order:
+                        ops.msolver_step_(x, eps, coefs[i].contiguous(), x0_logs[i], x0_logs[i - 1] if i else None,
+                                          eps_logs[i])
+                    else:
+                        ops.ddim_step_(x, eps, coefs[i].contiguous(), float(eta), x0_logs[i], eps_logs[i])
         logs["timesteps"] = [int(v) for v in times[:-1]]
         logs["pred_x0"] = list(x0_logs.unbind(0))
         logs["noise_pred"] = list(eps_logs.unbind(0))
@@ -436,3 +484,49 @@ class LDM(nn.Module):
     def content_style_ddim_sample(self, z_t, style_embedding, timesteps=250, eta=0.0):
         times = torch.linspace(timesteps - 1, 0, timesteps).long()              # (model.py:514)
         return self._reverse(z_t, style_embedding, times, eta)
+
+    # -------------------------------------------------------------------------------------------
+    # Samplers with a separate noise level (t_start) and step count, and a choice of solver.  The reference has
+    # no counterpart; its methods above are untouched.
+    _SOLVERS = {"ddim": 0, "dpmpp1": 1, "dpmpp2m": 2}
+
+    def sample_times(self, t_start, steps):
+        """The steps + 1 schedule indices linspace(t_start, 0) of a `steps`-step sampler from t_start."""
+        t_start, steps = int(t_start), int(steps)
+        if not 1 <= steps <= t_start <= self.num_timesteps - 1:
+            raise ValueError(f"sample_times: need 1 <= steps <= t_start <= {self.num_timesteps - 1}, got steps "
+                             f"{steps}, t_start {t_start} (with more steps than indices two times coincide)")
+        return torch.linspace(t_start, 0, steps + 1).long()
+
+    def _solve(self, z_t, style_embedding, times, solver, eta):
+        if solver not in self._SOLVERS:
+            raise ValueError(f"unknown solver {solver!r}: one of {sorted(self._SOLVERS)}")
+        return self._reverse(z_t, style_embedding, times, eta, order=self._SOLVERS[solver])
+
+    def style_conditioned_sample(self, z_t, style_embedding, steps=20, solver="dpmpp2m", t_start=None, eta=0.0):
+        """z_t at index t_start (default num_timesteps - 1) denoised in `steps` UNet passes over
+        sample_times(t_start, steps).  solver: "dpmpp2m" (DPM-Solver++(2M), first-order first and last step),
+        "dpmpp1" (its first-order form) or "ddim" (the reference's update, with eta, on this time grid).
+        Returns (x, logs) like style_conditioned_ddim_sample."""
+        t_start = self.num_timesteps - 1 if t_start is None else t_start
+        return self._solve(z_t, style_embedding, self.sample_times(t_start, steps), solver, eta)
+
+    def content_style_transfer(self, content_spec, style_spec, t_start=99, steps=10, solver="dpmpp2m", noise=None,
+                               eta=0.0):
+        """Encode content, q_sample it at index t_start (the strength), denoise over sample_times(t_start, steps)
+        with `solver`, decode.  Returns (decoded, z_t_decoded) like content_style_transfer_wrapper.
+
+        No equivalence with content_style_transfer_wrapper is promised, solver="ddim" included: the wrapper ties
+        noise level and step count together (its time grid is linspace(T' - 1, 0, T')), here they are separate
+        arguments and `steps` counts UNet passes, so the grids differ by design."""
+        content_spec = content_spec.float()
+        style_spec = style_spec.float()
+        times = self.sample_times(t_start, steps)
+        z_0 = self.encoder(content_spec)
+        t = torch.full((content_spec.shape[0],), int(t_start), dtype=torch.long)
+        z_t, noise = self.noise_scheduler(z_0, t.to(content_spec.device), noise=noise)
+        style_embedding = self.style_encoder(style_spec)
+        sampled, _ = self._solve(z_t, style_embedding, times, solver, eta)
+        decoded = self.decoder(sampled, rescale=True)
+        z_t_decoded = self.decoder(z_t)
+        return decoded, z_t_decoded

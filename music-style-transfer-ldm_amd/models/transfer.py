@@ -19,7 +19,7 @@ HOP = audio.N_FFT // 4
 
 
 def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, num_timesteps=100, eta=0.0,
-                       batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80):
+                       batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -29,12 +29,22 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     Content window n is paired with style window n mod Ns, Ns the style's full windows (overlap 0; its single padded
     window when it has no full one).  The q_sample noise of window n is row n of one CPU draw seeded with `seed`,
     whatever batch_size is.  ValueError for a recording shorter than n_fft / 2 + 1 samples, a bad window plan, or
-    num_timesteps beyond the model's schedule."""
+    num_timesteps beyond the model's schedule.
+
+    solver=None is the reference's sampler: num_timesteps is both the noise level (index num_timesteps - 1) and the
+    step count.  With solver "dpmpp2m", "dpmpp1" or "ddim" every window goes through LDM.content_style_transfer
+    instead: the content is noised at index t_start (default 99) and denoised in num_timesteps steps."""
     n_mels = 128
     for name, y in (("content", content), ("style", style)):
         if y.dim() != 1 or y.numel() < audio.N_FFT // 2 + 1:
             raise ValueError(f"transfer_recording: {name} must be a mono waveform [L] of at least "
                              f"{audio.N_FFT // 2 + 1} samples, got shape {tuple(y.shape)}")
+    if solver is None and t_start is not None:
+        raise ValueError("transfer_recording: t_start needs a solver (solver=None is the reference's sampler, whose "
+                         "noise level is num_timesteps - 1)")
+    if solver is not None:
+        t_start = 99 if t_start is None else int(t_start)
+        model.sample_times(t_start, num_timesteps)    # ValueError for a bad (t_start, steps) pair
     if not 1 <= num_timesteps <= model.num_timesteps:
         raise ValueError(f"transfer_recording: num_timesteps {num_timesteps} outside the model's schedule "
                          f"(1..{model.num_timesteps})")
@@ -58,8 +68,14 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     with torch.no_grad():
         for b0 in range(0, N, batch_size):
             b1 = min(b0 + batch_size, N)
-            decoded, _ = model.content_style_transfer_wrapper(x[b0:b1], xs[pair[b0:b1]], num_timesteps=num_timesteps,
-                                                              eta=eta, noise=noise[b0:b1])
+            if solver is None:
+                decoded, _ = model.content_style_transfer_wrapper(x[b0:b1], xs[pair[b0:b1]],
+                                                                  num_timesteps=num_timesteps, eta=eta,
+                                                                  noise=noise[b0:b1])
+            else:
+                decoded, _ = model.content_style_transfer(x[b0:b1], xs[pair[b0:b1]], t_start=t_start,
+                                                          steps=num_timesteps, solver=solver, eta=eta,
+                                                          noise=noise[b0:b1])
             out.append(decoded)
     windows_out = torch.cat(out)
     mel_power = longform.stitch_windows(windows_out, ref_db, overlap, T_total, max_db)
@@ -91,6 +107,11 @@ def parse_args(argv=None):
     p.add_argument("--overlap", type=int, default=64, help="mel frames two neighbouring windows share")
     p.add_argument("--steps", type=int, default=100, help="diffusion steps per window")
     p.add_argument("--eta", type=float, default=0.0)
+    p.add_argument("--solver", choices=("dpmpp2m", "dpmpp1", "ddim"), default=None,
+                   help="sample with this solver from --t-start in --steps steps (default: the reference's sampler, "
+                        "where --steps is also the noise level)")
+    p.add_argument("--t-start", type=int, default=None, dest="t_start",
+                   help="schedule index the content is noised at (needs --solver; default 99)")
     p.add_argument("--batch", type=int, default=8, help="windows per model call")
     p.add_argument("--seed", type=int, default=0)
     return p.parse_args(argv)
@@ -105,7 +126,8 @@ def main(argv=None):
     content, style = ap.trim_silence(content), ap.trim_silence(style)
     model = load_model(args.checkpoint)
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
-                             num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed)
+                             num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
+                             solver=args.solver, t_start=args.t_start)
     ap.save_wav(args.out, res.audio, sr)
     print(f"{args.out}: {res.audio.numel() / sr:.1f} s, {res.N} windows of {args.frames} frames "
           f"({math.ceil(res.N / args.batch)} model calls)")
