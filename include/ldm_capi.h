@@ -202,6 +202,19 @@ int ldm_attention_fold_keys(const float* kv, const float* wq, const float* bq, i
                             int32_t S, float scale, float* kf, float* bf, void* stream);
 int ldm_attention_folded(const float* z, const float* kv, const float* kf, const float* bf, float* out, int32_t B,
                          int32_t E, int32_t heads, int32_t L, int32_t S, void* stream);
+/* Style mixing: the folded attention over any key count S >= 1 (several style references stacked along the keys)
+ * with an optional additive key bias [B,S] (fp32; NULL = none; -inf removes a key, and a key run that is entirely
+ * -inf contributes exactly 0):  out(q) = sum_s exp(q.k_s + bias_s) v_s / sum_s exp(q.k_s + bias_s).
+ * Instances: E 256 and E 512 at 4 heads; any L >= 1.  S == L without a bias runs ldm_attention_folded; anything
+ * else streams the keys in tiles with an online softmax (stylemix.hip).  z, kf and out 16-byte aligned.
+ * ldm_attention_fold_keys_bias is ldm_attention_fold_keys with the bias added to bf (bf[b,h,s] += key_bias[b,s]),
+ * so an attention that reads this bf needs no bias argument; key_bias NULL is ldm_attention_fold_keys itself. */
+int ldm_attention_folded_keys(const float* z, const float* kv, const float* kf, const float* bf,
+                              const float* key_bias, float* out, int32_t B, int32_t E, int32_t heads, int32_t L,
+                              int32_t S, void* stream);
+int ldm_attention_fold_keys_bias(const float* kv, const float* wq, const float* bq, int32_t B, int32_t E,
+                                 int32_t heads, int32_t S, float scale, const float* key_bias, float* kf, float* bf,
+                                 void* stream);
 /* The folded attention's probabilities only: p [B,heads,L,S] = softmax(z^T kf_h + bf_h) (CA1's instance: E 512,
  * 4 heads, L, S <= 16).  The reverse loop's bottleneck then contracts them with its folded values (below). */
 int ldm_attention_folded_probs(const float* z, const float* kf, const float* bf, float* p, int32_t B, int32_t E,
@@ -376,6 +389,24 @@ int ldm_ddim_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x
 int ldm_msolver_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
                        const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps,
                        float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
+/* Style mixing: the same two loops attending over S5 / S6 style tokens per sample instead of the maps' own
+ * H*W/16 / H*W/64: s5 [B,256,S5], s6 [B,512,S6] (R references stacked along the map's height: reference r owns
+ * keys [r*L, (r+1)*L)), key_bias5 [B,S5] / key_bias6 [B,S6] as in ldm_attention_folded_keys (log of each
+ * reference's weight; NULL = none).  The K/V projections and the key fold run over S tokens, the bias is folded
+ * into bf once per loop, and each step's two attentions stream the keys.  Needs use_fold (an error otherwise);
+ * with S6 != H*W/64 or a key_bias6 the bottleneck runs without its value fold.  Workspace:
+ * ldm_ddim_workspace_floats_mix.  With S5 = H*W/16, S6 = H*W/64 and no bias these are ldm_ddim_sample /
+ * ldm_msolver_sample / ldm_ddim_workspace_floats. */
+int64_t ldm_ddim_workspace_floats_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5,
+                                      int32_t S6);
+int ldm_ddim_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                        const float* s6, int32_t S5, int32_t S6, const float* key_bias5, const float* key_bias6,
+                        const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta, float* x0_logs,
+                        float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
+int ldm_msolver_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                           const float* s6, int32_t S5, int32_t S6, const float* key_bias5, const float* key_bias6,
+                           const int64_t* t_table, const float* coef_table, int32_t nsteps, float* x0_logs,
+                           float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
 
 /* ---- data formats either side of the path (dataio.hip) ---------------------------
  * ldm_mel_quantize: the reference's 8-bit mel PNG pixels, uint8(clip((db + max_db) * 255/max_db, 0, 255)

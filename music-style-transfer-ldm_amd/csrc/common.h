@@ -216,6 +216,12 @@ int attention_fold_keys(const float* kv, const float* wq, const float* bq, int32
                         int32_t S, float scale, float* kf, float* bf, hipStream_t st);
 int attention_folded_probs(const float* z, const float* kf, const float* bf, float* p, int32_t B, int32_t E,
                            int32_t heads, int32_t L, int32_t S, hipStream_t st);
+// stylemix.hip: the folded attention for any key count S with an optional key bias [B,S] (key-tiled, online
+// softmax; S == L without a bias runs attention_folded), and attention_fold_keys with the bias added to bf
+int attention_folded_keys(const float* z, const float* kv, const float* kf, const float* bf, const float* key_bias,
+                          float* out, int32_t B, int32_t E, int32_t heads, int32_t L, int32_t S, hipStream_t st);
+int attention_fold_keys_bias(const float* kv, const float* wq, const float* bq, int32_t B, int32_t E, int32_t heads,
+                             int32_t S, float scale, const float* key_bias, float* kf, float* bf, hipStream_t st);
 // bfold.hip: the reverse loop's bottleneck with CA1's values folded into its weights (U, once per loop)
 bool bneck_fold_supported(int B, int H, int W);
 int bneck_fold_values(const float* wf, const float* kv, float* u, int B, hipStream_t st);

@@ -124,9 +124,13 @@ static bool use_bneck_fold(const ldm_unet_shape& s, const ldm_unet_weights* w) {
            bneck_fold_supported(s.B, s.H, s.W);
 }
 
-static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float* base) {
+// S5 / S6: key counts of CA2 / CA1 (style mixing: several references stacked along the keys); 0 = the map's own
+// token count, which is every caller but the *_mix loops.  Only the K/V projections and the folded keys scale.
+static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float* base, int64_t S5 = 0, int64_t S6 = 0) {
     const int64_t B = s.B, nf = s.nf, HW = (int64_t)s.H * s.W;
     const int64_t HW2 = HW / 4, L2 = HW / 16, L1 = HW / 64;
+    if (S5 <= 0) S5 = L2;
+    if (S6 <= 0) S6 = L1;
     UNetWs w{};
     int64_t off = 0;
     auto take = [&](int64_t n) {
@@ -140,12 +144,12 @@ static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float*
     w.z2 = take(B * 2 * nf * HW2);
     w.z3 = take(B * 4 * nf * L2);
     w.q2 = take(B * 256 * L2);
-    w.kv2 = take(B * 512 * L2);
+    w.kv2 = take(B * 512 * S5);
     w.a2 = take(B * 256 * L2);
     w.c2 = take(B * 256 * L2);
     w.z4 = take(B * 8 * nf * L1);
     w.q1 = take(B * 512 * L1);
-    w.kv1 = take(B * 1024 * L1);
+    w.kv1 = take(B * 1024 * S6);
     w.a1 = take(B * 512 * L1);
     w.c1 = take(B * 512 * L1);
     w.zb = take(B * 8 * nf * L1);
@@ -153,13 +157,13 @@ static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float*
     w.d3 = take(B * 2 * nf * HW2);
     w.d2 = take(B * nf * HW);
     w.eps = take(B * (int64_t)s.C * HW);
-    w.kf2 = take(B * 4 * 256 * L2);
-    w.bf2 = take(B * 4 * L2);
-    w.kf1 = take(B * 4 * 512 * L1);
-    w.bf1 = take(B * 4 * L1);
+    w.kf2 = take(B * 4 * 256 * S5);
+    w.bf2 = take(B * 4 * S5);
+    w.kf1 = take(B * 4 * 512 * S6);
+    w.bf1 = take(B * 4 * S6);
     w.xs = take(B * (int64_t)s.C * HW);
     w.uks = take(wts && wts->use_step ? step_ws_floats(s.B, s.H, s.W) : 0);
-    const bool bfold = use_bneck_fold(s, wts);
+    const bool bfold = use_bneck_fold(s, wts) && S6 == L1;   // (its kernels are built for 16 keys)
     w.ubn = take(bfold ? B * 512 * 576 : 0);
     w.p1 = take(bfold ? B * 4 * L1 * L1 : 0);
     w.total = off;
@@ -215,6 +219,25 @@ static int style_kv(const ldm_unet_shape& s, const ldm_unet_weights& w, const fl
     return 0;
 }
 
+// One K/V projection over S style tokens instead of the map's own count (style mixing).  The weights are packed
+// for the bound plan, and the pack depends on the plan's kernel kind and tile only, never on the token count:
+// the same kind and tile are forced for the longer row, without a K split (no workspace beyond the bound one).
+static int style_kv_tokens(const ldm_unet_shape& s, const ldm_unet_weights& w, int j, const float* sm, int S, float* kv,
+                           hipStream_t st) {
+    ldm_conv_desc d;
+    LDM_TRY(layer_desc(s, 10 + 3 * j, d));
+    d.Win = d.Wout = S;
+    const ldm_conv_plan& bound = w.ca_plan_kv[j];
+    LDM_REQUIRE(bound.kind >= 0 && bound.kind <= 2, "style mix: the K/V projection's plan must be a direct or fp32 MFMA plan");
+    ldm_conv_plan plan;
+    LDM_TRY(ldm_conv_make_plan_forced(&d, bound.kind, bound.tm, bound.tn, bound.wk, 1, &plan));
+    LDM_REQUIRE(plan.packed_floats == bound.packed_floats && plan.ws_floats == 0, "style mix: K/V projection plan mismatch");
+    EpiArgs ep{};
+    ep.bias = w.ca_bkv[j];
+    ep.act = 0;
+    return conv_forward_ex(d, plan, sm, w.ca_wkv[j], ep, kv, nullptr, st);
+}
+
 // kv_ready: ws.kv2 / ws.kv1 already hold style_kv() of these s5 / s6 (the reverse loop computes them
 // once, before its first step — the same kernel on the same inputs, so bitwise what each step's
 // in-loop projection would produce).
@@ -259,18 +282,18 @@ static int unet_forward(const ldm_unet_shape& s, const ldm_unet_weights& w, cons
 // out-projection into the following conv (ldm_fold_conv_proj, once per weight version).  11 launches per
 // step instead of 15; the same arithmetic up to fp32 re-association.
 static int unet_forward_folded(const ldm_unet_shape& s, const ldm_unet_weights& w, const float* z, const UNetWs& ws,
-                               hipStream_t st, const float* temb, const DdimFuse* fuse) {
+                               hipStream_t st, const float* temb, const DdimFuse* fuse, int S5, int S6) {
     const int HW = s.H * s.W;
     const int L2 = HW / 16, L1 = HW / 64;
     LDM_TRY(conv_call(s, ws.convws, 0, w.conv_plan[0], z, w.conv_w[0], w.conv_b[0], LDM_ACT_RELU, nullptr, nullptr, ws.z1, st));
     LDM_TRY(conv_call(s, ws.convws, 1, w.conv_plan[1], ws.z1, w.conv_w[1], w.conv_b[1], LDM_ACT_RELU, temb, nullptr, ws.z2, st));
     LDM_TRY(conv_call(s, ws.convws, 2, w.conv_plan[2], ws.z2, w.conv_w[2], w.conv_b[2], LDM_ACT_RELU, nullptr, nullptr, ws.z3, st));
     // cross_attention2 then enc4 (model.py:211-212)
-    LDM_TRY(attention_folded(ws.z3, ws.kv2, ws.kf2, ws.bf2, ws.a2, s.B, 256, 4, L2, L2, st));
+    LDM_TRY(attention_folded_keys(ws.z3, ws.kv2, ws.kf2, ws.bf2, nullptr, ws.a2, s.B, 256, 4, L2, S5, st));
     LDM_TRY(conv_call(s, ws.convws, 3, w.conv_plan[3], ws.a2, w.fold_w[0], nullptr, LDM_ACT_RELU, nullptr, nullptr, ws.z4, st,
                       nullptr, w.fold_pb[0]));
     // cross_attention1 then bottleneck (model.py:214-217)
-    LDM_TRY(attention_folded(ws.z4, ws.kv1, ws.kf1, ws.bf1, ws.a1, s.B, 512, 4, L1, L1, st));
+    LDM_TRY(attention_folded_keys(ws.z4, ws.kv1, ws.kf1, ws.bf1, nullptr, ws.a1, s.B, 512, 4, L1, S6, st));
     LDM_TRY(conv_call(s, ws.convws, 4, w.conv_plan[4], ws.a1, w.fold_w[1], nullptr, LDM_ACT_RELU, nullptr, nullptr, ws.zb, st,
                       nullptr, w.fold_pb[1]));
     LDM_TRY(conv_call(s, ws.convws, 5, w.conv_plan[5], ws.zb, w.conv_w[5], w.conv_b[5], LDM_ACT_RELU, nullptr, ws.z3, ws.d4, st));
@@ -284,7 +307,7 @@ static int unet_forward_folded(const ldm_unet_shape& s, const ldm_unet_weights& 
 // The same folded step on the step kernels (uconv.hip): x and every activation NHWC, 11 launches, the
 // DDIM update fused into dec1.  z (the sampler state) is ws.xs.
 static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w, const UNetWs& ws, hipStream_t st,
-                             const float* temb, const DdimFuse& fuse) {
+                             const float* temb, const DdimFuse& fuse, int S5, int S6, bool bfold) {
     const int HW = s.H * s.W;
     const int L2 = HW / 16, L1 = HW / 64;
     // the nine convs' operands: enc1..enc3, enc4 (after CA2), bottleneck (after CA1), dec4..dec2, dec1 + DDIM
@@ -317,16 +340,16 @@ static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w,
         return 0;
     };
     LDM_TRY(run(0, 2));
-    LDM_TRY(attention_folded(ws.z3, ws.kv2, ws.kf2, ws.bf2, ws.a2, s.B, 256, 4, L2, L2, st));
+    LDM_TRY(attention_folded_keys(ws.z3, ws.kv2, ws.kf2, ws.bf2, nullptr, ws.a2, s.B, 256, 4, L2, S5, st));
     LDM_TRY(run(3, 3));
-    if (use_bneck_fold(s, &w)) {
+    if (bfold) {
         // CA1's probabilities, then the bottleneck on its folded values U (formed before the loop)
         if (ca1_probs_own()) LDM_TRY(ca1_probs(ws.z4, ws.kf1, ws.bf1, ws.p1, s.B, st));
         else LDM_TRY(attention_folded_probs(ws.z4, ws.kf1, ws.bf1, ws.p1, s.B, 512, 4, L1, L1, st));
         LDM_TRY(bneck_pv(ws.ubn, ws.p1, w.step_pb[1], ws.zb, s.B, w.step_dtype, st));
         return run(5, 8);
     }
-    LDM_TRY(attention_folded(ws.z4, ws.kv1, ws.kf1, ws.bf1, ws.a1, s.B, 512, 4, L1, L1, st));
+    LDM_TRY(attention_folded_keys(ws.z4, ws.kv1, ws.kf1, ws.bf1, nullptr, ws.a1, s.B, 512, 4, L1, S6, st));
     return run(4, 8);
 }
 
@@ -374,10 +397,22 @@ extern "C" int ldm_unet_forward(const ldm_unet_shape* s, const ldm_unet_weights*
 
 // The reverse loop of both samplers.  msolver: coef_table is [nsteps, 8] (multistep rows) and every step i > 0 reads
 // step i-1's slot of x0_logs as its history (a first-order row there carries c_1 = 0); step 0 has none to read.
+// Style mixing (S5 / S6 > 0 and key_bias5 / key_bias6, the *_mix entries): s5 / s6 hold S5 / S6 style tokens per
+// sample, the K/V projections and the key fold run over them, the bias goes into the folded keys' bias, and the
+// two attention launches of each step stream the keys (stylemix.hip).  With the maps' own counts and no bias every
+// call below is the one it always was.
 static int sample_loop(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
                        const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta, float* x0_logs,
-                       float* eps_logs, int64_t log_step_stride, float* workspace, void* stream, bool msolver) {
-    UNetWs ws = carve(*s, w, workspace);
+                       float* eps_logs, int64_t log_step_stride, float* workspace, void* stream, bool msolver,
+                       int32_t S5 = 0, int32_t S6 = 0, const float* key_bias5 = nullptr,
+                       const float* key_bias6 = nullptr) {
+    const int L2 = s->H * s->W / 16, L1 = s->H * s->W / 64;
+    if (S5 <= 0) S5 = L2;
+    if (S6 <= 0) S6 = L1;
+    const bool mix = S5 != L2 || S6 != L1 || key_bias5 || key_bias6;
+    LDM_REQUIRE(!mix || w->use_fold, "style mix: the reverse loop attends over several references only with the "
+                                     "folded cross-attentions (use_fold)");
+    UNetWs ws = carve(*s, w, workspace, S5, S6);
     float* temb_all = workspace + ws.total;   // [nsteps*B, 128] (ldm_ddim_workspace_floats)
     const int64_t dense = (int64_t)s->B * s->C * s->H * s->W;
     LDM_REQUIRE(log_step_stride == 0 || log_step_stride >= dense, "ddim_sample: log stride smaller than a step");
@@ -389,27 +424,34 @@ static int sample_loop(const ldm_unet_shape* s, const ldm_unet_weights* w, float
     LDM_TRY(ldm_time_mlp_forward(t_table, 0, nsteps * s->B, 128, w->t_freqs, w->t_w1, w->t_b1, w->t_w2, w->t_b2,
                                  temb_all, st));
     // Likewise the style maps' K/V projections (model.py:153 with kv = s5 / s6, fixed for the loop).
-    LDM_TRY(style_kv(*s, *w, s5, s6, ws, st));
+    if (S5 == L2 && S6 == L1) {
+        LDM_TRY(style_kv(*s, *w, s5, s6, ws, st));
+    } else {
+        LDM_TRY(style_kv_tokens(*s, *w, 0, s5, S5, ws.kv2, st));
+        LDM_TRY(style_kv_tokens(*s, *w, 1, s6, S6, ws.kv1, st));
+    }
     const int HW = s->H * s->W;
     if (w->use_fold) {
         LDM_REQUIRE(w->ca_wq_raw[0] && w->ca_wq_raw[1] && w->fold_w[0] && w->fold_w[1] && w->fold_pb[0] && w->fold_pb[1],
                     "ddim_sample: use_fold needs the folded weights");
-        LDM_TRY(attention_fold_keys(ws.kv2, w->ca_wq_raw[0], w->ca_bq[0], s->B, 256, 4, HW / 16,
-                                    (float)std::sqrt(1.0 / 64.0), ws.kf2, ws.bf2, st));
-        LDM_TRY(attention_fold_keys(ws.kv1, w->ca_wq_raw[1], w->ca_bq[1], s->B, 512, 4, HW / 64,
-                                    (float)std::sqrt(1.0 / 128.0), ws.kf1, ws.bf1, st));
+        LDM_TRY(attention_fold_keys_bias(ws.kv2, w->ca_wq_raw[0], w->ca_bq[0], s->B, 256, 4, S5,
+                                         (float)std::sqrt(1.0 / 64.0), key_bias5, ws.kf2, ws.bf2, st));
+        LDM_TRY(attention_fold_keys_bias(ws.kv1, w->ca_wq_raw[1], w->ca_bq[1], s->B, 512, 4, S6,
+                                         (float)std::sqrt(1.0 / 128.0), key_bias6, ws.kf1, ws.bf1, st));
         if (w->use_step) {
             LDM_REQUIRE(s->C == 32 && s->nf == 64, "ddim_sample: the step kernels are built for latent 32 / 64 filters");
             for (int l = 0; l < 9; ++l) LDM_REQUIRE(w->step_w[l], "ddim_sample: use_step needs the step weights");
             LDM_REQUIRE(w->step_pb[0] && w->step_pb[1], "ddim_sample: use_step needs the folded biases");
             LDM_REQUIRE(w->step_dtype >= LDM_DT_F32 && w->step_dtype <= LDM_DT_BF16, "ddim_sample: step_dtype");
-            if (use_bneck_fold(*s, w)) LDM_TRY(bneck_fold_values(w->step_bneck_w, ws.kv1, ws.ubn, s->B, st));
+            // the bottleneck's value fold is built for CA1's own 16 keys without a bias: a mix leaves it
+            const bool bfold = use_bneck_fold(*s, w) && S6 == L1 && !key_bias6;
+            if (bfold) LDM_TRY(bneck_fold_values(w->step_bneck_w, ws.kv1, ws.ubn, s->B, st));
             LDM_TRY(step_layout(x, ws.xs, s->B, s->C, HW, true, st));
             for (int i = 0; i < nsteps; ++i) {
                 DdimFuse fuse{coef_table + cw * (size_t)i, eta, ws.xs, x0_logs ? x0_logs + (size_t)i * n : nullptr,
                               eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
                               msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
-                LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse));
+                LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold));
             }
             return step_layout(ws.xs, x, s->B, s->C, HW, false, st);
         }
@@ -417,7 +459,7 @@ static int sample_loop(const ldm_unet_shape* s, const ldm_unet_weights* w, float
             DdimFuse fuse{coef_table + cw * (size_t)i, eta, x, x0_logs ? x0_logs + (size_t)i * n : nullptr,
                           eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
                           msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
-            LDM_TRY(unet_forward_folded(*s, *w, x, ws, st, temb_all + (size_t)i * s->B * 128, &fuse));
+            LDM_TRY(unet_forward_folded(*s, *w, x, ws, st, temb_all + (size_t)i * s->B * 128, &fuse, S5, S6));
         }
         return 0;
     }
@@ -461,4 +503,42 @@ extern "C" int ldm_msolver_sample(const ldm_unet_shape* s, const ldm_unet_weight
 extern "C" int64_t ldm_ddim_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps) {
     if (!s || nsteps < 0) return -1;
     return carve(*s, w, nullptr).total + (int64_t)nsteps * s->B * 128;
+}
+
+// ---- style mixing: the same loops over S5 / S6 style tokens per sample with an optional key bias ----------------
+static int mix_args_ok(const ldm_unet_shape* s, int32_t S5, int32_t S6) {
+    LDM_REQUIRE(s && S5 > 0 && S6 > 0, "style mix: key counts must be positive");
+    return 0;
+}
+
+extern "C" int64_t ldm_ddim_workspace_floats_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps,
+                                                 int32_t S5, int32_t S6) {
+    if (!s || nsteps < 0 || S5 <= 0 || S6 <= 0) return -1;
+    return carve(*s, w, nullptr, S5, S6).total + (int64_t)nsteps * s->B * 128;
+}
+
+extern "C" int ldm_ddim_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                                   const float* s6, int32_t S5, int32_t S6, const float* key_bias5,
+                                   const float* key_bias6, const int64_t* t_table, const float* coef_table,
+                                   int32_t nsteps, float eta, float* x0_logs, float* eps_logs, int64_t log_step_stride,
+                                   float* workspace, void* stream) {
+    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace, "ddim_sample_mix: null argument");
+    LDM_REQUIRE(nsteps >= 0, "ddim_sample_mix: negative step count");
+    LDM_TRY(mix_args_ok(s, S5, S6));
+    if (nsteps == 0) return 0;
+    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, eta, x0_logs, eps_logs, log_step_stride, workspace,
+                       stream, false, S5, S6, key_bias5, key_bias6);
+}
+
+extern "C" int ldm_msolver_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                                      const float* s6, int32_t S5, int32_t S6, const float* key_bias5,
+                                      const float* key_bias6, const int64_t* t_table, const float* coef_table,
+                                      int32_t nsteps, float* x0_logs, float* eps_logs, int64_t log_step_stride,
+                                      float* workspace, void* stream) {
+    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace && x0_logs, "msolver_sample_mix: null argument");
+    LDM_REQUIRE(nsteps >= 0, "msolver_sample_mix: negative step count");
+    LDM_TRY(mix_args_ok(s, S5, S6));
+    if (nsteps == 0) return 0;
+    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs, log_step_stride, workspace,
+                       stream, true, S5, S6, key_bias5, key_bias6);
 }

@@ -201,6 +201,19 @@ SIGNATURES = {
                                   c_fp, c_int32, c_float, c_fp, c_fp, c_int64, c_fp, c_vp]),
     "ldm_msolver_sample": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp, c_vp,
                                      c_fp, c_int32, c_fp, c_fp, c_int64, c_fp, c_vp]),
+    # style mixing (stylemix.hip, unet.hip): key-tiled folded attention with a key bias, and the loops over S5 / S6 keys
+    "ldm_attention_folded_keys": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_int32, c_int32,
+                                            c_int32, c_vp]),
+    "ldm_attention_fold_keys_bias": (c_int32, [c_fp, c_fp, c_fp, c_int32, c_int32, c_int32, c_int32, c_float, c_fp,
+                                               c_fp, c_fp, c_vp]),
+    "ldm_ddim_workspace_floats_mix": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_int32,
+                                                c_int32, c_int32]),
+    "ldm_ddim_sample_mix": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
+                                      c_int32, c_int32, c_fp, c_fp, c_vp, c_fp, c_int32, c_float, c_fp, c_fp, c_int64,
+                                      c_fp, c_vp]),
+    "ldm_msolver_sample_mix": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
+                                         c_int32, c_int32, c_fp, c_fp, c_vp, c_fp, c_int32, c_fp, c_fp, c_int64, c_fp,
+                                         c_vp]),
     # backward / optimiser
     "ldm_conv_tiled_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),
     "ldm_conv_sconv_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),

@@ -194,14 +194,18 @@ class UNetEngine:
         self._bound[skey] = (vkey, w)
         return w
 
-    def workspace(self, shape, device, nsteps=0, slot=0):
+    def workspace(self, shape, device, nsteps=0, slot=0, keys=None):
         """Workspace for this shape and its bound plans; `slot` separates concurrently running sub-batch
-        chains.  Zero-filled on allocation: it carries the split-K tile counters (ldm_capi.h)."""
+        chains.  Zero-filled on allocation: it carries the split-K tile counters (ldm_capi.h).
+        keys = (S5, S6): the style-mixing loops' workspace for those key counts (a buffer of its own)."""
         w = self.weights(shape)
-        n = L.load().ldm_ddim_workspace_floats(byref(shape), byref(w), int(nsteps))
+        if keys is None:
+            n = L.load().ldm_ddim_workspace_floats(byref(shape), byref(w), int(nsteps))
+        else:
+            n = L.load().ldm_ddim_workspace_floats_mix(byref(shape), byref(w), int(nsteps), int(keys[0]), int(keys[1]))
         if n <= 0:
             raise RuntimeError("ldm_ddim_workspace_floats failed")
-        key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot)
+        key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot) + (tuple(keys) if keys else ())
         ws = self._ws.get(key)
         if ws is None or ws.numel() < n:
             ws = torch.zeros(int(n), device=device, dtype=torch.float32)
@@ -233,6 +237,9 @@ class UNetEngine:
         z, s5, s6 = ops.f32c(z), ops.f32c(s5), ops.f32c(s6)
         B, C, H, W = z.shape
         shape = self.shape(B, C, H, W)
+        if self.mix_keys(z, s5, s6) is not None:
+            raise RuntimeError("UNetEngine.forward: several style references (stacked style maps) are attended over in "
+                               "the reverse loop only (ddim_loop / msolver_loop with the folded cross-attentions)")
         if tuple(s5.shape) != (B, 256, H // 4, W // 4) or tuple(s6.shape) != (B, 512, H // 8, W // 8):
             raise RuntimeError(f"UNet: style maps must be s5 [B,256,H/4,W/4], s6 [B,512,H/8,W/8] for z {tuple(z.shape)}; "
                                f"got {tuple(s5.shape)}, {tuple(s6.shape)}")
@@ -248,27 +255,82 @@ class UNetEngine:
                s6.data_ptr(), y.data_ptr(), ws.data_ptr(), ops.stream_handle())
         return y
 
-    def _ddim_call(self, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot):
+    @staticmethod
+    def mix_keys(x, s5, s6, key_bias5=None, key_bias6=None):
+        """(S5, S6), the key counts of a style mix: style maps holding R references stacked along the height (s5
+        [B,256,R*H/4,W/4], s6 [B,512,R*H/8,W/8]) and / or a key bias.  None for today's single maps."""
+        B, C, H, W = x.shape
+        if s5.dim() != 4 or s6.dim() != 4:
+            return None
+        S5, S6 = s5.shape[2] * s5.shape[3], s6.shape[2] * s6.shape[3]
+        if key_bias5 is None and key_bias6 is None and S5 == (H // 4) * (W // 4) and S6 == (H // 8) * (W // 8):
+            return None
+        return S5, S6
+
+    def _mix_check(self, x, s5, s6, key_bias5, key_bias6):
+        """Validates a style mix's operands and returns (S5, S6, bias pointers); raises where no mixing path exists."""
+        B, C, H, W = x.shape
+        S5, S6 = self.mix_keys(x, s5, s6, key_bias5, key_bias6)
+        L2, L1 = (H // 4) * (W // 4), (H // 8) * (W // 8)
+        if tuple(s5.shape[:2]) != (B, 256) or tuple(s6.shape[:2]) != (B, 512) or S5 % L2 or S6 % L1 or \
+                S5 // L2 != S6 // L1 or s5.shape[3] != W // 4 or s6.shape[3] != W // 8:
+            raise RuntimeError(f"style mix: style maps must be s5 [B,256,R*H/4,W/4], s6 [B,512,R*H/8,W/8] with one R for "
+                               f"z {tuple(x.shape)}; got {tuple(s5.shape)}, {tuple(s6.shape)}")
+        if not (self.fold and self.fold_applies(self.shape(B, C, H, W))):
+            raise RuntimeError("style mix: several style references need the folded cross-attentions (fold=True, "
+                               "latent planes up to 1024 positions); the unfolded engine has no kernel for them")
+        ptrs = []
+        for kb, S, name in ((key_bias5, S5, "key_bias5"), (key_bias6, S6, "key_bias6")):
+            if kb is None:
+                ptrs.append(None)
+                continue
+            ops.require_device(kb, what=name)
+            if kb.dtype != torch.float32 or tuple(kb.shape) != (B, S) or not kb.is_contiguous():
+                raise RuntimeError(f"style mix: {name} must be a contiguous fp32 [{B},{S}] tensor, got "
+                                   f"{kb.dtype} {tuple(kb.shape)}")
+            ptrs.append(kb.data_ptr())
+        return S5, S6, ptrs[0], ptrs[1]
+
+    def _ddim_call(self, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5=None,
+                   key_bias6=None):
         B, C, H, W = x.shape
         shape = self.shape(B, C, H, W)
-        w = self.weights(shape)
         n = t_table.shape[0]
+        if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
+            S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
+            w = self.weights(shape)
+            ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6))
+            L.call("ldm_ddim_sample_mix", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(), S5, S6,
+                   p5, p6, t_table.data_ptr(), coef_table.data_ptr(), n, float(eta), ops._p(x0_logs), ops._p(eps_logs),
+                   int(log_stride), ws.data_ptr(), ops.stream_handle())
+            return
+        w = self.weights(shape)
         ws = self.workspace(shape, x.device, n, slot)
         L.call("ldm_ddim_sample", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(),
                t_table.data_ptr(), coef_table.data_ptr(), n, float(eta), ops._p(x0_logs), ops._p(eps_logs),
                int(log_stride), ws.data_ptr(), ops.stream_handle())
 
-    def _msolver_call(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs, log_stride, slot):
+    def _msolver_call(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs, log_stride, slot, key_bias5=None,
+                      key_bias6=None):
         B, C, H, W = x.shape
         shape = self.shape(B, C, H, W)
-        w = self.weights(shape)
         n = t_table.shape[0]
+        if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
+            S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
+            w = self.weights(shape)
+            ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6))
+            L.call("ldm_msolver_sample_mix", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(), S5, S6,
+                   p5, p6, t_table.data_ptr(), coef_table.data_ptr(), n, x0_logs.data_ptr(), ops._p(eps_logs),
+                   int(log_stride), ws.data_ptr(), ops.stream_handle())
+            return
+        w = self.weights(shape)
         ws = self.workspace(shape, x.device, n, slot)
         L.call("ldm_msolver_sample", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(),
                t_table.data_ptr(), coef_table.data_ptr(), n, x0_logs.data_ptr(), ops._p(eps_logs), int(log_stride),
                ws.data_ptr(), ops.stream_handle())
 
-    def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None):
+    def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None, key_bias5=None,
+                     key_bias6=None):
         """ddim_loop's twin for the multistep solver (DPM-Solver++(2M) or its first-order form): coef_table
         [n,8] from ForwardDiffusion.multistep_coefs (device), no eta.  x0_logs [n,B,C,H,W] is required: step i
         reads step i-1's slot as its history.  Same sub-batch chains as ddim_loop."""
@@ -278,11 +340,18 @@ class UNetEngine:
             raise ValueError(f"msolver_loop: coef_table must be [n,8] for n = {t_table.shape[0]} steps, "
                              f"got {tuple(coef_table.shape)}")
         return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
-                          lambda xs, a5, a6, t, x0l, epl, stride, slot:
-                          self._msolver_call(xs, a5, a6, t, coef_table, x0l, epl, stride, slot))
+                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None:
+                          self._msolver_call(xs, a5, a6, t, coef_table, x0l, epl, stride, slot, b5, b6),
+                          key_bias5, key_bias6)
 
-    def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None):
+    def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None,
+                  key_bias5=None, key_bias6=None):
         """In-place reverse loop on x ([B,C,H,W] contiguous fp32).  t_table [n,B] int64, coef [n,4] (device).
+
+        Style mixing: s5 / s6 may hold R style references stacked along the map's height (s5 [B,256,R*H/4,W/4],
+        s6 [B,512,R*H/8,W/8]; reference r owns keys [r*L, (r+1)*L)), with key_bias5 [B,R*H*W/16] / key_bias6
+        [B,R*H*W/64] (fp32, the log of each key's reference weight, -inf allowed; None = equal weights).  Needs the
+        folded engine; the sub-batch split slices the biases with the maps.
 
         split > 1 runs the batch as that many independent sub-batch chains, each on its own stream
         (forked from and joined back into the current stream, so it also works under graph capture).
@@ -290,17 +359,24 @@ class UNetEngine:
         size may get a conv plan that splits K differently); the chains' launch and memory latencies
         overlap each other's work."""
         return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
-                          lambda xs, a5, a6, t, x0l, epl, stride, slot:
-                          self._ddim_call(xs, a5, a6, t, coef_table, eta, x0l, epl, stride, slot))
+                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None:
+                          self._ddim_call(xs, a5, a6, t, coef_table, eta, x0l, epl, stride, slot, b5, b6),
+                          key_bias5, key_bias6)
 
-    def _loop(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call):
+    def _loop(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5=None, key_bias6=None):
         """The whole batch in one C call, or one per sub-batch chain; call(x, s5, s6, t, x0_logs, eps_logs,
-        log_stride, slot) is one sampler's C call."""
+        log_stride, slot[, key_bias5, key_bias6]) is one sampler's C call."""
         B = x.shape[0]
+        keys = self.mix_keys(x, s5, s6, key_bias5, key_bias6)
+        if keys is not None:
+            self._mix_check(x, s5, s6, key_bias5, key_bias6)
         if plan is None:
             plan = self.split_plan(t_table, B, split) if split > 1 else None
         if not plan or len(plan) == 1:
-            call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0)
+            if keys is None:
+                call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0)
+            else:
+                call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6)
             return x
         per_step = x[0].numel() * B
         main = torch.cuda.current_stream(x.device)
@@ -309,16 +385,21 @@ class UNetEngine:
         for k, (lo, hi, t_sub) in enumerate(plan):   # bind / pack / allocate on the main stream first
             shape = self.shape(hi - lo, C, H, W)
             self.weights(shape)
-            self.workspace(shape, x.device, t_table.shape[0], k)
+            self.workspace(shape, x.device, t_table.shape[0], k, keys=keys)
         for k, (lo, hi, t_sub) in enumerate(plan):
             st = streams[k]
             st.wait_stream(main)
             if not torch.cuda.is_current_stream_capturing():
                 t_sub.record_stream(st)
             with torch.cuda.stream(st):
-                call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub,
-                     None if x0_logs is None else x0_logs[0, lo:hi],
-                     None if eps_logs is None else eps_logs[0, lo:hi], per_step, k)
+                x0l = None if x0_logs is None else x0_logs[0, lo:hi]
+                epl = None if eps_logs is None else eps_logs[0, lo:hi]
+                if keys is None:
+                    call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, x0l, epl, per_step, k)
+                else:   # the biases are split with the maps (leading-dimension slices stay contiguous)
+                    call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, x0l, epl, per_step, k,
+                         None if key_bias5 is None else key_bias5[lo:hi],
+                         None if key_bias6 is None else key_bias6[lo:hi])
         for st in streams:
             main.wait_stream(st)
         return x
@@ -327,9 +408,11 @@ class UNetEngine:
 class GraphedDDIM:
     """A captured reverse loop with static buffers: replay() re-runs all n steps from x_init."""
 
-    def __init__(self, engine, x_init, s5, s6, t_table, coef_table, eta, logs=True, split=1, solver="ddim"):
+    def __init__(self, engine, x_init, s5, s6, t_table, coef_table, eta, logs=True, split=1, solver="ddim",
+                 key_bias5=None, key_bias6=None):
         """solver="ddim": coef_table [n,4] and eta, the reference's update; solver="msolver": coef_table [n,8]
-        (ForwardDiffusion.multistep_coefs), eta unused and the x0 logs always kept (the solver's history)."""
+        (ForwardDiffusion.multistep_coefs), eta unused and the x0 logs always kept (the solver's history).
+        s5 / s6 may be stacked style references with key_bias5 / key_bias6 (UNetEngine.ddim_loop)."""
         if solver not in ("ddim", "msolver"):
             raise ValueError(f"GraphedDDIM: unknown solver {solver!r}")
         self.solver = solver
@@ -341,6 +424,8 @@ class GraphedDDIM:
         self.x = torch.empty_like(self.x_init)
         self.s5 = s5.contiguous().clone()
         self.s6 = s6.contiguous().clone()
+        self.kb5 = None if key_bias5 is None else key_bias5.contiguous().clone()
+        self.kb6 = None if key_bias6 is None else key_bias6.contiguous().clone()
         self.t_table = t_table.to(dev).contiguous()
         self.coef = coef_table.to(dev).contiguous()
         n = self.t_table.shape[0]
@@ -372,21 +457,23 @@ class GraphedDDIM:
                 self.x[lo:hi].copy_(self.x_init[lo:hi])
                 x0l = None if self.x0_logs is None else self.x0_logs[0, lo:hi]
                 epl = None if self.eps_logs is None else self.eps_logs[0, lo:hi]
+                kb5 = None if self.kb5 is None else self.kb5[lo:hi]
+                kb6 = None if self.kb6 is None else self.kb6[lo:hi]
                 if solver == "msolver":
                     engine._msolver_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, x0l, epl,
-                                         per_step, k)
+                                         per_step, k, kb5, kb6)
                 else:
                     engine._ddim_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
-                                      x0l, epl, per_step, k)
+                                      x0l, epl, per_step, k, kb5, kb6)
             self.graphs.append(g)
 
     def _run(self, plan=None):
         if self.solver == "msolver":
             self.engine.msolver_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.x0_logs, self.eps_logs,
-                                     plan=plan)
+                                     plan=plan, key_bias5=self.kb5, key_bias6=self.kb6)
         else:
             self.engine.ddim_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.eta, self.x0_logs,
-                                  self.eps_logs, plan=plan)
+                                  self.eps_logs, plan=plan, key_bias5=self.kb5, key_bias6=self.kb6)
 
     def replay(self):
         if self.streams is None:

@@ -329,6 +329,11 @@ class UNet(nn.Module):
 
     def forward(self, z, t, style_embedding: dict = None):
         s5, s6 = style_embedding["s5"], style_embedding["s6"]
+        if style_embedding.get("refs", 1) > 1 or style_embedding.get("key_bias5") is not None or \
+                style_embedding.get("key_bias6") is not None:
+            raise RuntimeError("UNet.forward: a style embedding of several references (LDM.encode_styles) is attended "
+                               "over in the samplers' fused reverse loop only; the single forward, the per-layer path "
+                               "and training take one style map per sample")
         if HF._needs_grad(z, s5, s6, *self.parameters()) or not UNetEngine.supports(z.shape[1]):
             return self._layerwise(z, t, s5, s6)
         return engine_for(self).forward(z, t, s5, s6)
@@ -434,14 +439,26 @@ class LDM(nn.Module):
         eps_logs = torch.empty_like(x0_logs)
         s5 = ops.f32c(style_embedding["s5"])
         s6 = ops.f32c(style_embedding["s6"])
+        kb5, kb6 = style_embedding.get("key_bias5"), style_embedding.get("key_bias6")
+        mix = UNetEngine.mix_keys(x, s5, s6, kb5, kb6) is not None   # several references (encode_styles)
         coefs = coefs.to(dev)
         with torch.no_grad():
-            if UNetEngine.supports(x.shape[1]):
+            if UNetEngine.supports(x.shape[1]) and mix:
+                eng = engine_for(self.unet)
+                if order:
+                    eng.msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs, key_bias5=kb5, key_bias6=kb6)
+                else:
+                    eng.ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs, key_bias5=kb5,
+                                  key_bias6=kb6)
+            elif UNetEngine.supports(x.shape[1]):
                 if order:
                     engine_for(self.unet).msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs)
                 else:
                     engine_for(self.unet).ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs)
             else:   # latent widths the fused engine does not take: per-layer UNet + the update kernel
+                if mix:
+                    raise RuntimeError(f"style mix: latent width {x.shape[1]} runs the per-layer path, which takes one "
+                                       "style map per sample (the fused engine needs a multiple of 8, at least 16)")
                 emb = {"s5": s5, "s6": s6}
                 for i in range(n):
                     eps = self.unet(x, t_table[i], emb)
@@ -455,6 +472,68 @@ class LDM(nn.Module):
         logs["noise_pred"] = list(eps_logs.unbind(0))
         return x, logs
 
+    MAX_STYLE_REFS = 8
+
+    @staticmethod
+    def normalise_style_weights(weights, R, B=None):
+        """Host-side checks of style weights: a float64 CPU tensor [R] or [B,R], each row non-negative with a
+        positive sum, scaled to sum 1.  ValueError otherwise."""
+        w = torch.as_tensor(weights, dtype=torch.float64).detach().cpu()
+        if w.dim() not in (1, 2) or w.shape[-1] != R or (w.dim() == 2 and B is not None and w.shape[0] != B):
+            raise ValueError(f"style weights must be [{R}] or [B,{R}] for {R} references, got {tuple(w.shape)}")
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError("style weights must be finite and non-negative")
+        tot = w.sum(-1, keepdim=True)
+        if bool((tot <= 0).any()):
+            raise ValueError("style weights: every sample needs at least one positive weight")
+        return w / tot
+
+    def encode_styles(self, style_specs, weights=None):
+        """Style embedding of R weighted references per sample: style_specs [B,R,1,n_mels,F], weights [R] or [B,R]
+        (default equal; normalised to sum 1).  The style encoder runs once on the B*R maps; the result's s5 / s6
+        hold the references stacked along the map's height (reference r owns the keys [r*L, (r+1)*L)) and
+        key_bias5 / key_bias6 [B,R*L] the log of each key's reference weight (None for equal weights), which the
+        samplers add to the cross-attentions' scores: softmax over all references' keys, reference r scaled by w_r.
+        A zero column of an [R] weight vector is dropped before anything runs; a zero in [B,R] weights becomes a
+        -inf bias (that sample ignores the reference).  R = 1 is the plain embedding."""
+        if style_specs.dim() != 5:
+            raise ValueError(f"encode_styles: style_specs must be [B,R,1,n_mels,F], got {tuple(style_specs.shape)}")
+        B, R = style_specs.shape[:2]
+        if not 1 <= R <= self.MAX_STYLE_REFS:
+            raise ValueError(f"encode_styles: 1 to {self.MAX_STYLE_REFS} style references, got {R}")
+        w = None
+        if weights is not None:
+            w = self.normalise_style_weights(weights, R, B)
+            if w.dim() == 1:
+                keep = torch.nonzero(w > 0).flatten()
+                if keep.numel() < R:
+                    style_specs = style_specs[:, keep.to(style_specs.device)]
+                    w, R = w[keep], int(keep.numel())
+        specs = style_specs.float().reshape((B * R,) + tuple(style_specs.shape[2:]))
+        emb = self.style_encoder(specs)
+        out = {"refs": R, "key_bias5": None, "key_bias6": None}
+        for k in ("s5", "s6"):
+            m = emb[k]
+            if R == 1:
+                out[k] = m
+                continue
+            c, h, wd = m.shape[1:]
+            out[k] = m.reshape(B, R, c, h, wd).permute(0, 2, 1, 3, 4).reshape(B, c, R * h, wd).contiguous()
+        if w is not None and R > 1:
+            logw = torch.log(w if w.dim() == 2 else w.view(1, R).expand(B, R)).float()   # log 0 = -inf
+            for k, name in (("s5", "key_bias5"), ("s6", "key_bias6")):
+                L = out[k].shape[2] * out[k].shape[3] // R
+                out[name] = logw.repeat_interleave(L, dim=1).contiguous().to(out[k].device)
+        return out
+
+    def _style_embedding(self, style_spec, style_weights=None):
+        """The style embedding of a 4-D map (today's) or of 5-D stacked references with optional weights."""
+        if style_spec.dim() == 5:
+            return self.encode_styles(style_spec, style_weights)
+        if style_weights is not None:
+            raise ValueError("style_weights needs a 5-D style_spec [B,R,1,n_mels,F]")
+        return self.style_encoder(style_spec)
+
     def style_ddim_sample_wrapper(self, z_shape, style_spec, timesteps=100, eta=0.0):
         z_t = torch.randn(z_shape).to(style_spec.device)            # CPU generator (model.py:394)
         style_embedding = self.style_encoder(style_spec)
@@ -465,7 +544,8 @@ class LDM(nn.Module):
         times = torch.linspace(self.num_timesteps - 1, 0, timesteps).long()    # (model.py:420)
         return self._reverse(z_t, style_embedding, times, eta)
 
-    def content_style_transfer_wrapper(self, content_spec, style_spec, num_timesteps=250, eta=0.0, noise=None):
+    def content_style_transfer_wrapper(self, content_spec, style_spec, num_timesteps=250, eta=0.0, noise=None,
+                                       style_weights=None):
         """Encode content, q_sample it at T'-1, run the T'-step content/style loop, decode (reference
         model.py:468-501).  `noise` (optional, [B, latent, H/8, W/8]) injects the q_sample epsilon that
         the reference draws with randn_like (parity tests); by default it is drawn on the device."""
@@ -475,7 +555,7 @@ class LDM(nn.Module):
         t = torch.full((content_spec.shape[0],), num_timesteps - 1, dtype=torch.long)
         self.noise_scheduler._check_t(t)                                        # IndexError like model.py:107
         z_t, noise = self.noise_scheduler(z_0, t.to(content_spec.device), noise=noise)
-        style_embedding = self.style_encoder(style_spec)
+        style_embedding = self._style_embedding(style_spec, style_weights)   # 5-D: several references (encode_styles)
         sampled, _ = self.content_style_ddim_sample(z_t, style_embedding, num_timesteps, eta)
         decoded = self.decoder(sampled, rescale=True)
         z_t_decoded = self.decoder(z_t)
@@ -512,20 +592,25 @@ class LDM(nn.Module):
         return self._solve(z_t, style_embedding, self.sample_times(t_start, steps), solver, eta)
 
     def content_style_transfer(self, content_spec, style_spec, t_start=99, steps=10, solver="dpmpp2m", noise=None,
-                               eta=0.0):
+                               eta=0.0, style_weights=None):
         """Encode content, q_sample it at index t_start (the strength), denoise over sample_times(t_start, steps)
         with `solver`, decode.  Returns (decoded, z_t_decoded) like content_style_transfer_wrapper.
 
         No equivalence with content_style_transfer_wrapper is promised, solver="ddim" included: the wrapper ties
         noise level and step count together (its time grid is linspace(T' - 1, 0, T')), here they are separate
-        arguments and `steps` counts UNet passes, so the grids differ by design."""
+        arguments and `steps` counts UNet passes, so the grids differ by design.
+
+        style_spec [B,R,1,n_mels,F] with style_weights ([R] or [B,R], default equal) attends over R weighted
+        style references (encode_styles)."""
+        if style_weights is not None and style_spec.dim() != 5:
+            raise ValueError("style_weights needs a 5-D style_spec [B,R,1,n_mels,F]")
         content_spec = content_spec.float()
         style_spec = style_spec.float()
         times = self.sample_times(t_start, steps)
         z_0 = self.encoder(content_spec)
         t = torch.full((content_spec.shape[0],), int(t_start), dtype=torch.long)
         z_t, noise = self.noise_scheduler(z_0, t.to(content_spec.device), noise=noise)
-        style_embedding = self.style_encoder(style_spec)
+        style_embedding = self._style_embedding(style_spec, style_weights)
         sampled, _ = self._solve(z_t, style_embedding, times, solver, eta)
         decoded = self.decoder(sampled, rescale=True)
         z_t_decoded = self.decoder(z_t)

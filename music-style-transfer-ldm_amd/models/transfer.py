@@ -3,6 +3,7 @@ goes through LDM.content_style_transfer_wrapper paired with a window of the styl
 are crossfaded into one mel spectrogram that is vocoded once, so the phase is continuous across the seams.
 
     python -m models.transfer --content a.wav --style b.wav --out c.wav [--checkpoint ldm.pth]
+    python -m models.transfer --content a.wav --style b.wav c.wav --style-weights 0.7 0.3 --style-refs 2 --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
 """
@@ -18,8 +19,20 @@ from ldm_amd import audio, longform
 HOP = audio.N_FFT // 4
 
 
+def style_window_indices(Ns, refs):
+    """The `refs` style windows taken from a recording with Ns full windows: evenly spaced from the first to the last,
+    index round(i (Ns - 1) / (refs - 1)), halves rounding up; a single window is index 0."""
+    Ns, refs = int(Ns), int(refs)
+    if Ns < 1 or refs < 1:
+        raise ValueError(f"style_window_indices: need Ns >= 1 and refs >= 1, got {Ns}, {refs}")
+    if refs == 1:
+        return [0]
+    return [int(math.floor(i * (Ns - 1) / (refs - 1) + 0.5)) for i in range(refs)]
+
+
 def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, num_timesteps=100, eta=0.0,
-                       batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None):
+                       batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None,
+                       style_weights=None, style_refs=1):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -33,9 +46,24 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
 
     solver=None is the reference's sampler: num_timesteps is both the noise level (index num_timesteps - 1) and the
     step count.  With solver "dpmpp2m", "dpmpp1" or "ddim" every window goes through LDM.content_style_transfer
-    instead: the content is noised at index t_start (default 99) and denoised in num_timesteps steps."""
+    instead: the content is noised at index t_start (default 99) and denoised in num_timesteps steps.
+
+    Style mixing: `style` may be a list of waveforms, style_refs windows are taken from each (style_window_indices),
+    and every content window attends over all of them at once (LDM.encode_styles) instead of being paired with one.
+    style_weights: one weight per recording, or [N, recordings] per content window (a morph along the recording);
+    default equal.  A recording's weight is shared equally among its windows.  At most LDM.MAX_STYLE_REFS windows
+    in all.  One recording, style_refs = 1 and no weights is the cyclic pairing above, unchanged."""
     n_mels = 128
-    for name, y in (("content", content), ("style", style)):
+    styles = list(style) if isinstance(style, (list, tuple)) else [style]
+    if not styles:
+        raise ValueError("transfer_recording: no style recording")
+    style_refs = int(style_refs)
+    mixing = len(styles) > 1 or style_refs != 1 or style_weights is not None
+    if style_refs < 1 or len(styles) * style_refs > model.MAX_STYLE_REFS:
+        raise ValueError(f"transfer_recording: {len(styles)} recordings x style_refs {style_refs} must give 1 to "
+                         f"{model.MAX_STYLE_REFS} style windows")
+    style = styles[0]
+    for name, y in [("content", content)] + [("style", y) for y in styles]:
         if y.dim() != 1 or y.numel() < audio.N_FFT // 2 + 1:
             raise ValueError(f"transfer_recording: {name} must be a mono waveform [L] of at least "
                              f"{audio.N_FFT // 2 + 1} samples, got shape {tuple(y.shape)}")
@@ -63,6 +91,36 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     latent = model.unet.enc1.weight.shape[1]
     noise = torch.randn((N, latent, n_mels // 8, frames // 8), generator=torch.Generator().manual_seed(int(seed)))
     noise = noise.to(content.device)
+    if mixing:
+        refs = [xs[style_window_indices(Ns, style_refs)]]
+        for y in styles[1:]:
+            Pr = audio.melspectrogram(y, sr=sr, n_mels=n_mels)
+            xr, _ = longform.mel_windows(Pr, frames, 0, max_db)
+            refs.append(xr[style_window_indices(max(1, Pr.shape[-1] // frames), style_refs)])
+        refs = torch.cat(refs)                                  # [R, 1, n_mels, frames], recording-major
+        w = None
+        if style_weights is not None:
+            w = torch.as_tensor(style_weights, dtype=torch.float64).detach().cpu()
+            if w.dim() not in (1, 2) or w.shape[-1] != len(styles) or (w.dim() == 2 and w.shape[0] != N):
+                raise ValueError(f"transfer_recording: style_weights must be [{len(styles)}] (one per recording) or "
+                                 f"[{N}, {len(styles)}] (per content window), got {tuple(w.shape)}")
+            model.normalise_style_weights(w, len(styles))              # the checks; encode_styles normalises
+            w = w.repeat_interleave(style_refs, dim=-1) / style_refs   # shared equally among a recording's windows
+        out = []
+        with torch.no_grad():
+            for b0 in range(0, N, batch_size):
+                b1 = min(b0 + batch_size, N)
+                spec = refs.unsqueeze(0).expand((b1 - b0,) + tuple(refs.shape))
+                wb = None if w is None else (w if w.dim() == 1 else w[b0:b1])
+                if solver is None:
+                    decoded, _ = model.content_style_transfer_wrapper(x[b0:b1], spec, num_timesteps=num_timesteps,
+                                                                      eta=eta, noise=noise[b0:b1], style_weights=wb)
+                else:
+                    decoded, _ = model.content_style_transfer(x[b0:b1], spec, t_start=t_start, steps=num_timesteps,
+                                                              solver=solver, eta=eta, noise=noise[b0:b1],
+                                                              style_weights=wb)
+                out.append(decoded)
+        return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N)
     pair = torch.arange(N, device=content.device) % Ns
     out = []
     with torch.no_grad():
@@ -77,6 +135,10 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                                                           steps=num_timesteps, solver=solver, eta=eta,
                                                           noise=noise[b0:b1])
             out.append(decoded)
+    return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N)
+
+
+def _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N):
     windows_out = torch.cat(out)
     mel_power = longform.stitch_windows(windows_out, ref_db, overlap, T_total, max_db)
     y = audio.mel_to_audio(mel_power, sr=sr, n_iter=n_iter, nnls_iters=nnls_iters, seed=seed, length=Ln)
@@ -100,7 +162,13 @@ def load_model(checkpoint=None, device="cuda"):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="python -m models.transfer", description=__doc__.split("\n\n")[0])
     p.add_argument("--content", required=True, help="the recording to transfer (.wav, PCM16 or float32, any rate)")
-    p.add_argument("--style", required=True, help="the recording whose style is applied (.wav)")
+    p.add_argument("--style", required=True, nargs="+",
+                   help="the recording whose style is applied (.wav); several files are mixed")
+    p.add_argument("--style-weights", type=float, nargs="+", default=None, dest="style_weights",
+                   help="one non-negative weight per --style file (default equal)")
+    p.add_argument("--style-refs", type=int, default=1, dest="style_refs",
+                   help="windows taken from each style recording, evenly spaced; with more than one window in all, "
+                        "every content window attends over all of them")
     p.add_argument("--out", required=True, help="the .wav to write (mono PCM16 at 22050 Hz)")
     p.add_argument("--checkpoint", default=None, help="a full ldm.pth state dict (default: untrained weights)")
     p.add_argument("--frames", type=int, default=512, help="mel frames per window")
@@ -114,7 +182,14 @@ def parse_args(argv=None):
                    help="schedule index the content is noised at (needs --solver; default 99)")
     p.add_argument("--batch", type=int, default=8, help="windows per model call")
     p.add_argument("--seed", type=int, default=0)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.style_weights is not None and len(args.style_weights) != len(args.style):
+        p.error(f"--style-weights: {len(args.style_weights)} weights for {len(args.style)} --style files")
+    if args.style_refs < 1:
+        p.error("--style-refs must be positive")
+    if len(args.style) == 1:
+        args.style = args.style[0]      # a single file: the string it always was
+    return args
 
 
 def main(argv=None):
@@ -122,12 +197,15 @@ def main(argv=None):
     from data.audio_processor import AudioPreprocessor
     ap = AudioPreprocessor()
     content, sr = ap.load_audio_native(args.content)
-    style, _ = ap.load_audio_native(args.style)
-    content, style = ap.trim_silence(content), ap.trim_silence(style)
+    files = [args.style] if isinstance(args.style, str) else list(args.style)
+    styles = [ap.trim_silence(ap.load_audio_native(f)[0]) for f in files]
+    content = ap.trim_silence(content)
+    style = styles[0] if len(styles) == 1 else styles
     model = load_model(args.checkpoint)
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
                              num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
-                             solver=args.solver, t_start=args.t_start)
+                             solver=args.solver, t_start=args.t_start, style_weights=args.style_weights,
+                             style_refs=args.style_refs)
     ap.save_wav(args.out, res.audio, sr)
     print(f"{args.out}: {res.audio.numel() / sr:.1f} s, {res.N} windows of {args.frames} frames "
           f"({math.ceil(res.N / args.batch)} model calls)")
