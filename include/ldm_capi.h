@@ -407,6 +407,47 @@ int ldm_msolver_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, f
                            const float* s6, int32_t S5, int32_t S6, const float* key_bias5, const float* key_bias6,
                            const int64_t* t_table, const float* coef_table, int32_t nsteps, float* x0_logs,
                            float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
+/* Style guidance: the same two loops steered from a base style towards the target.  Every step evaluates the
+ * denoiser under both conditions on the same x and t and steps on
+ *   eps = e_b + scale[b] * (e_t - e_b)          (fp32, one rounding per operation: d = e_t - e_b; g = s d; e = e_b + g)
+ * with e_t / e_b dec1's outputs (after its output rounding with 16-bit operands); eps feeds the unchanged DDIM /
+ * multistep update, the logs ([n, B, C, H, W]) record the guided x0 / eps, and the multistep history is the guided
+ * x0.  scale = 1 is the unguided sampler on the target up to one rounding, scale = 0 the one on the base.
+ * s->B is the caller's batch B; x is [B, C, H, W] in and out; s5 / s6 (target) and s5_base / s6_base are separate
+ * [B, ...] maps with the same key counts S5 / S6 (0 = the maps' own, else as in the *_mix entries, which needs
+ * use_fold), each with its optional key biases; guide_scale is a device array [B] of finite fp32.  The body runs the
+ * UNet at batch 2B (targets, then bases): w holds the plans and weights bound for the shape with batch 2B
+ * (ldm_unet_make_plans on it).  One exception is allowed with use_step: the plans may be those of a larger batch (a
+ * sub-batch chain running the whole batch's plans, so that a sample's arithmetic does not depend on how a batch is
+ * split), provided the two K/V projection plans need no split-K workspace (ws_floats == 0): a plan's kind, tile and
+ * weight pack do not depend on the batch, the grids come from s, and those two projections are the step-kernel
+ * path's only planned launches.  Without use_step dec1's bound plan must be of kind 0, 1 or 2 (what
+ * ldm_unet_make_plans produces); another kind is an error.
+ * The workspace is ldm_ddim_workspace_floats_guided's, more than twice the unguided one.  The entries take no size, so
+ * before anything is launched they ask the runtime for the extent of the device allocation that holds `workspace`
+ * and report an error if it ends before the guided size (a buffer sized by ldm_ddim_workspace_floats).  That is exact
+ * for a buffer that is an allocation of its own; one carved out of a larger pool is only known to end inside the
+ * pool, and the check is skipped under stream capture (run the loop eagerly once before capturing it).
+ * dec1 runs as two launches at batch B: the base half as a plain conv, the target half with the guidance and the
+ * update fused, storing the new state for both halves.
+ * ldm_guide_eps: the same arithmetic on whole tensors, out[i] = e_b[i] + scale[i / per_sample] * (e_t[i] - e_b[i])
+ * for B * per_sample elements (out may alias e_t or e_b). */
+int64_t ldm_ddim_workspace_floats_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5,
+                                         int32_t S6);
+int ldm_ddim_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                           const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
+                           const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
+                           const float* key_bias6_base, const float* guide_scale, const int64_t* t_table,
+                           const float* coef_table, int32_t nsteps, float eta, float* x0_logs, float* eps_logs,
+                           int64_t log_step_stride, float* workspace, void* stream);
+int ldm_msolver_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                              const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
+                              const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
+                              const float* key_bias6_base, const float* guide_scale, const int64_t* t_table,
+                              const float* coef_table, int32_t nsteps, float* x0_logs, float* eps_logs,
+                              int64_t log_step_stride, float* workspace, void* stream);
+int ldm_guide_eps(const float* e_t, const float* e_b, const float* scale, int64_t per_sample, int32_t B, float* out,
+                  void* stream);
 
 /* ---- data formats either side of the path (dataio.hip) ---------------------------
  * ldm_mel_quantize: the reference's 8-bit mel PNG pixels, uint8(clip((db + max_db) * 255/max_db, 0, 255)

@@ -192,6 +192,13 @@ struct EpiArgs {
     // ddim_x0_log (required: the solver's history) / ddim_eps_log are the sampler state and logs as above
     const float* ms_coef;      // [8] {alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0} or NULL
     const float* ms_x0_prev;   // the previous step's x0 log (laid out like ddim_x0_log), or NULL: first-order step
+    // style guidance in front of either fused update (guide_eps): this launch is the target-conditioned half of the
+    // reverse loop's doubled batch; guide_eb holds the base-conditioned noise prediction (laid out like ddim_x),
+    // guide_scale one strength per sample of this launch, and the new state also goes to ddim_x2 (the base half's
+    // copy of the sampler state).  NULL guide_eb: no guidance.
+    const float* guide_eb;
+    const float* guide_scale;
+    float* ddim_x2;
 };
 
 // conv.hip: implicit-GEMM conv with the full internal epilogue (incl. the fused DDIM update); y may be
@@ -243,6 +250,13 @@ struct StepConv {
     int msolver;          // dec1: the multistep update (coef = an 8-float row, x0_log required) instead of DDIM's
     const float* x0_prev; // dec1, msolver: the previous step's x0 log (NCHW), or NULL for a first-order step
     int dtype;            // operand precision: LDM_DT_F32 / LDM_DT_F16 / LDM_DT_BF16 (uconv.hip)
+    // dec1 of the guided loop (two launches at the caller's batch): plain = the base half as a conv without an
+    // update, y (NHWC) receiving e_b; guide_eb / guide_scale [B] / xs2 = the target half, which guides its output
+    // against e_b (guide_eps), updates xs and stores the new state to xs2 (the base half's copy) as well
+    int plain;
+    const float* guide_eb;
+    const float* guide_scale;
+    float* xs2;
     float* ws;            // split-K workspace (step_ws_floats; zero-filled once) for the K-split layers
 };
 int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st);
@@ -293,6 +307,16 @@ __device__ __forceinline__ float msolver_update(float xv, float e, const float* 
         xn = xn + t2;
     }
     return xn;
+}
+
+// Style guidance for one element: the noise prediction extrapolated from the base-conditioned e_b towards the
+// target-conditioned e_t by the strength s, with the same rounding discipline (s = 1 gives e_t up to one rounding,
+// e_t == e_b gives e_b exactly for every finite s).  Its result feeds ddim_update / msolver_update unchanged.
+__device__ __forceinline__ float guide_eps(float e_t, float e_b, float s) {
+#pragma clang fp contract(off)
+    const float d = e_t - e_b;
+    const float g = s * d;
+    return e_b + g;
 }
 
 // v rounded to a 16-bit type (LDM_DT_F16 / LDM_DT_BF16, round to nearest even), or unchanged (0)

@@ -1644,6 +1644,8 @@ int conv_forward_ex(const ldm_conv_desc& d, const ldm_conv_plan& p, const float*
     LDM_REQUIRE(!ep.ddim_coef || ep.ddim_x, "conv forward: fused DDIM update needs x");
     LDM_REQUIRE(!ep.ms_coef || (ep.ddim_x && ep.ddim_x0_log && !ep.ddim_coef && ep.ms_x0_prev != ep.ddim_x0_log),
                 "conv forward: fused multistep update needs x and its x0 log, and excludes the DDIM one");
+    LDM_REQUIRE(!ep.guide_eb || ((ep.ddim_coef || ep.ms_coef) && ep.guide_scale && ep.ddim_x2),
+                "conv forward: style guidance goes in front of a fused update and needs its scales and second state");
     if (p.kind == 3) return tconv_forward(d, p, x, w, ep, y, st);
     if (p.kind == 4) return sconv_forward(d, p, x, w, ep, y, st);
     ConvArgs a;

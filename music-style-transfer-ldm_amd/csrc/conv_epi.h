@@ -1,6 +1,6 @@
 // ConvArgs and the conv epilogue (conv.hip's implicit-GEMM kernels and sconv.hip's small-plane kernel share them):
 // the reference's op order conv + bias -> BN(eval) -> act -> + bcast -> + skip (model.py:16-25, :205-229), with
-// autocast output rounding and the fused DDIM / multistep-solver update.
+// autocast output rounding and the fused DDIM / multistep-solver update, optionally behind style guidance.
 #pragma once
 #include "common.h"
 
@@ -119,10 +119,18 @@ __device__ __forceinline__ void epi_finish(const ConvArgs& a, int m, size_t oidx
     if (e.act_out) e.act_out[oidx] = v;
     if (e.bcast) v = round16(v + p.bcast, ro);
     if (e.skip) v = round16(v + p.skip, ro);
+    float* x2 = nullptr;
+    if (e.guide_eb) {   // style guidance (uniform): v is the target half's prediction, guided against the base half's
+        const size_t per = (size_t)a.Cout * a.Hout * a.Wout;
+        v = guide_eps(v, e.guide_eb[oidx], e.guide_scale[oidx / per]);
+        x2 = e.ddim_x2;
+    }
     if (e.ms_coef) {   // the multistep solver's update (uniform branches; its history is read here, not prefetched)
         const bool hp = e.ms_x0_prev != nullptr;
         float x0;
-        e.ddim_x[oidx] = msolver_update(p.x, v, e.ms_coef, hp, hp ? e.ms_x0_prev[oidx] : 0.f, x0);
+        const float xn = msolver_update(p.x, v, e.ms_coef, hp, hp ? e.ms_x0_prev[oidx] : 0.f, x0);
+        e.ddim_x[oidx] = xn;
+        if (x2) x2[oidx] = xn;
         e.ddim_x0_log[oidx] = x0;
         if (e.ddim_eps_log) e.ddim_eps_log[oidx] = v;
         if (a.y) a.y[oidx] = v;
@@ -130,7 +138,9 @@ __device__ __forceinline__ void epi_finish(const ConvArgs& a, int m, size_t oidx
     }
     if (e.ddim_coef) {
         float x0;
-        e.ddim_x[oidx] = ddim_update(p.x, v, e.ddim_coef, e.ddim_eta, x0);
+        const float xn = ddim_update(p.x, v, e.ddim_coef, e.ddim_eta, x0);
+        e.ddim_x[oidx] = xn;
+        if (x2) x2[oidx] = xn;
         if (e.ddim_x0_log) e.ddim_x0_log[oidx] = x0;
         if (e.ddim_eps_log) e.ddim_eps_log[oidx] = v;
         if (a.y) a.y[oidx] = v;

@@ -621,6 +621,16 @@ __global__ __launch_bounds__(256) void msolver_step_kernel(float* __restrict__ x
     if (eps_log) eps_log[i] = e;
 }
 
+// Style guidance on whole tensors (the per-layer sampling path): out = guide_eps(e_t, e_b, scale[sample]).  out may
+// be e_t or e_b.
+__global__ __launch_bounds__(256) void guide_eps_kernel(const float* e_t, const float* e_b,
+                                                        const float* __restrict__ scale, int64_t per_sample, int64_t n,
+                                                        float* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = guide_eps(e_t[i], e_b[i], scale[i / per_sample]);
+}
+
 // (train-mode BatchNorm2d lives in reduce.hip)
 
 __global__ __launch_bounds__(256) void activation_kernel(const float* x, float* y, int64_t n, int act) {
@@ -905,6 +915,16 @@ extern "C" int ldm_msolver_step(float* x, const float* eps, const float* coef, c
     hipLaunchKernelGGL(msolver_step_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, eps, coef,
                        x0_prev, x0_log, eps_log, n);
     LDM_CHECK_LAUNCH("msolver_step_kernel");
+    return 0;
+}
+
+extern "C" int ldm_guide_eps(const float* e_t, const float* e_b, const float* scale, int64_t per_sample, int32_t B,
+                             float* out, void* stream) {
+    LDM_REQUIRE(e_t && e_b && scale && out && per_sample > 0 && B > 0, "guide_eps: bad argument");
+    const int64_t n = per_sample * B;
+    hipLaunchKernelGGL(guide_eps_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, e_t, e_b, scale,
+                       per_sample, n, out);
+    LDM_CHECK_LAUNCH("guide_eps_kernel");
     return 0;
 }
 

@@ -41,9 +41,13 @@
 namespace ldm {
 namespace uc {
 
-enum : int { EPI_RELU = 1, EPI_BCAST = 2, EPI_SKIP = 4, EPI_POSB = 8, EPI_DDIM = 16, EPI_PLANE = 32, EPI_WINDOW = 64, EPI_MSOLVER = 128 };
+enum : int { EPI_RELU = 1, EPI_BCAST = 2, EPI_SKIP = 4, EPI_POSB = 8, EPI_DDIM = 16, EPI_PLANE = 32, EPI_WINDOW = 64, EPI_MSOLVER = 128, EPI_GUIDE = 256 };
 // EPI_MSOLVER: dec1's epilogue is the multistep solver's update (msolver_update) in place of EPI_DDIM's; its
 // instances are separate ones, so the EPI_DDIM instances are compiled exactly as without it.
+// EPI_GUIDE (with EPI_DDIM or EPI_MSOLVER, again as separate instances): dec1 of the guided loop's target half.  The
+// launch covers the caller's B samples; the base half's noise prediction e_b (written just before by the same
+// geometry as a plain conv, NHWC) and the sample's strength are prefetched with the other epilogue operands, the
+// output becomes guide_eps(o, e_b, s) before the update, and the new state is stored to both halves' copies.
 // EPI_PLANE (a geometry flag carried with the epilogue bits): the layer's plane is 2 x 8 (the bottleneck at the
 // canonical 16 x 64 latent), so the 16 columns of a lane group are one sample's whole plane and every tap of a
 // stride-1 3x3 conv reads a position some lane of the group already holds.  Each channel chunk's activation
@@ -78,6 +82,9 @@ struct UArgs {
     int32_t* cnt;         // KS > 1: arrival counter per tile (zero between launches)
     const float* x0_prev; // EPI_MSOLVER: the previous step's pred_x0 log (NCHW like x0_log), or NULL (first-order step);
                           // coef is then the [8] row {alpha_t, sigma_t, c_x, c_0, c_1, ...} and x0_log is required
+    // EPI_GUIDE adds no field (the kernarg block of every step launch stays the size it was): it reads the base half's
+    // noise prediction (NHWC like xs) from `skip`, the guidance strength per sample [B] from `bcast`, and stores the
+    // base half's copy of the sampler state through `y`: the three slots dec1's fused update leaves unused
 };
 
 // (ky, kx) of tap t and the conv input offset / the transposed conv's output parity
@@ -352,7 +359,8 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
         o.ok = f < NFR && colsel(cval, ni) != 0;
         return o;
     };
-    floatx4 pre_b[NMY], pre_c[NMY], pre_s[NMY], pre_h[NMY];
+    floatx4 pre_b[NMY], pre_c[NMY], pre_s[NMY], pre_h[NMY], pre_g[NMY];
+    float pre_gs[NMY];
     auto epi_prefetch = [&]() {
         static_for<0, NMY>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
@@ -371,6 +379,10 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) pre_h[k][r] = a.x0_prev[lbase + r * hw];
                 }
+            }
+            if constexpr ((EPI & EPI_GUIDE) != 0) {
+                pre_g[k] = *reinterpret_cast<const floatx4*>(a.skip + (size_t)o.pix * COUT + o.m);
+                pre_gs[k] = a.bcast[o.b];
             }
         });
     };
@@ -701,6 +713,11 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = round16(o[r] + pre_s[k][r], DT);
         }
+        if constexpr ((EPI & EPI_GUIDE) != 0) {
+            // o is the target half's noise prediction: guided against the base half's (guide_eps), fp32 whatever DT is
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] = guide_eps(o[r], pre_g[k][r], pre_gs[k]);
+        }
         if constexpr ((EPI & EPI_MSOLVER) != 0) {
             // noise_pred = o; the multistep update (msolver_update, one rounding per op), fp32 whatever DT is
             const floatx4 xv = pre_s[k];
@@ -716,6 +733,7 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
                 if (a.eps_log) a.eps_log[lbase + r * hw] = o[r];
             }
             *reinterpret_cast<floatx4*>(a.xs + (size_t)ot.pix * COUT + ot.m) = xn;
+            if constexpr ((EPI & EPI_GUIDE) != 0) *reinterpret_cast<floatx4*>(a.y + (size_t)ot.pix * COUT + ot.m) = xn;
         } else if constexpr ((EPI & EPI_DDIM) != 0) {
             // noise_pred = o; the reverse update of model.py:442-458 (ddim_update, one rounding per op)
             const floatx4 xv = pre_s[k];
@@ -730,6 +748,7 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
                 if (a.eps_log) a.eps_log[lbase + r * hw] = o[r];
             }
             *reinterpret_cast<floatx4*>(a.xs + (size_t)ot.pix * COUT + ot.m) = xn;
+            if constexpr ((EPI & EPI_GUIDE) != 0) *reinterpret_cast<floatx4*>(a.y + (size_t)ot.pix * COUT + ot.m) = xn;
         } else {
             *reinterpret_cast<floatx4*>(a.y + (size_t)ot.pix * COUT + ot.m) = o;
         }
@@ -778,6 +797,7 @@ __global__ __launch_bounds__(256) void uconv_pack_kernel(const float* __restrict
         reinterpret_cast<__bf16*>(outp)[idx] = (__bf16)v;
 }
 
+#ifndef UCONV_GUIDE_TU
 // NCHW <-> NHWC for the sampler state (once before / after the loop)
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, int C,
                                                            int HW, int64_t n) {
@@ -799,6 +819,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
     const int64_t b = r / C;
     y[idx] = x[(b * HW + p) * C + c];
 }
+#endif
 
 // ------------------------------------------------------------------------------------------------------
 // Layer table: the instance each of the nine layers runs (the batch only changes the grid).
@@ -846,6 +867,35 @@ static int launch(const UArgs& a, int dtype, hipStream_t st) {
         default: return fail(2, "step conv: unknown operand precision");
     }
 }
+
+// dec1's two launches in the guided loop live in a translation unit of their own (uconv_guide.hip: this file compiled
+// with UCONV_GUIDE_TU, which keeps the templates and this dispatcher only), so that the code object of the unguided
+// step kernels holds exactly the instances it held without guidance.  geo: 0 variant 3 windowed, 1 / 2 the thin form
+// with / without the window, 3 / 4 the 32-row form with / without it.
+int step_dec1_guided(int geo, const UArgs& a, const StepConv& s, hipStream_t st);
+#ifdef UCONV_GUIDE_TU
+// on geometry (TM, TN, WN, WK, NCH, S; GEO = EPI_WINDOW or 0): the base half as a plain conv, or the target half with
+// the guided DDIM / multistep update
+template <int TM, int TN, int WN, int WK, int NCH, int S, int GEO, int KS = 1>
+static int launch_dec1_guided(const UArgs& a, const StepConv& s, hipStream_t st) {
+    if (s.plain) return launch<0, 64, 32, TM, TN, WN, WK, NCH, S, GEO, KS>(a, s.dtype, st);
+    LDM_REQUIRE(s.xs && s.coef, "dec1 (guided): sampler state, coefficients");
+    if (s.msolver) return launch<0, 64, 32, TM, TN, WN, WK, NCH, S, EPI_MSOLVER | EPI_GUIDE | GEO, KS>(a, s.dtype, st);
+    return launch<0, 64, 32, TM, TN, WN, WK, NCH, S, EPI_DDIM | EPI_GUIDE | GEO, KS>(a, s.dtype, st);
+}
+int step_dec1_guided(int geo, const UArgs& a, const StepConv& s, hipStream_t st) {
+    switch (geo) {
+        case 0: return launch_dec1_guided<1, 2, 2, 4, 9, 9, EPI_WINDOW, 1>(a, s, st);
+        case 1: return launch_dec1_guided<1, 2, 2, 2, 18, 18, EPI_WINDOW>(a, s, st);
+        case 2: return launch_dec1_guided<1, 2, 2, 2, 18, 18, 0>(a, s, st);
+        case 3: return launch_dec1_guided<2, 2, 1, 4, 9, 9, EPI_WINDOW>(a, s, st);
+        case 4: return launch_dec1_guided<2, 2, 1, 4, 9, 9, 0>(a, s, st);
+        default: return fail(2, "step conv: unknown guided dec1 geometry");
+    }
+}
+}  // namespace uc
+}  // namespace ldm
+#else
 
 // The K-split form of the deep layers (variant 1): a 32 x 32 block tile (2 x 2 MFMA tiles per wave) instead of
 // 16 x 16, so a block pulls half the operand bytes per MFMA, with K split over KS blocks to keep 256 blocks
@@ -1112,6 +1162,7 @@ static int make_args(int layer, int B, int H, int W, const StepConv& s, int ksv,
     a.eps_log = s.eps_log;
     a.eta = s.eta;
     a.x0_prev = s.x0_prev;
+    if (s.guide_eb) a.skip = s.guide_eb, a.bcast = s.guide_scale, a.y = s.xs2;   // (EPI_GUIDE's slots, see UArgs)
     a.B = B;
     a.Hin = Hin;
     a.Win = Win;
@@ -1162,12 +1213,16 @@ static int make_args(int layer, int B, int H, int W, const StepConv& s, int ksv,
                 "step conv: tensor too large for 32-bit buffer offsets");
     LDM_REQUIRE(s.x && s.w && s.bias, "step conv: null operand");
     LDM_REQUIRE(!s.msolver || (layer == 8 && s.x0_log), "step conv: the multistep update is dec1's and needs its x0 log");
+    LDM_REQUIRE((!s.plain && !s.guide_eb) || layer == 8, "step conv: the guided loop's two launches are dec1's");
+    LDM_REQUIRE(!s.plain || (s.y && !s.guide_eb), "step conv: dec1's base half is a plain conv into y");
+    LDM_REQUIRE(!s.guide_eb || (s.guide_scale && s.xs2 && s.xs2 != s.xs), "step conv: guidance needs its scales and second state");
     return 0;
 }
 }  // namespace uc
 
 int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st) {
     using namespace uc;
+    const bool guided = s.plain || s.guide_eb;
     const int ksv = s.ws ? ks_form(layer, s.dtype, H, W) : 0;   // without a workspace: the single-block form
     UArgs a;
     UC_TRY(make_args(layer, B, H, W, s, ksv, a));
@@ -1184,7 +1239,9 @@ int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st)
                 return launch<2, 256, 128, 1, 1, 1, 16, 9, 9, EPI_RELU | EPI_SKIP | EPI_WINDOW, 1>(a, s.dtype, st);
             case 7: LDM_REQUIRE(s.y && s.skip && win && a.Wq % 32 == 0, "dec2 (variant 3): y, skip, 32-column rows");
                 return launch<2, 128, 64, 1, 2, 1, 8, 9, 9, EPI_RELU | EPI_SKIP | EPI_WINDOW, 1>(a, s.dtype, st);
-            case 8: LDM_REQUIRE(s.xs && s.coef && win && a.Wq % 64 == 0, "dec1 (variant 3): sampler state, 64-column rows");
+            case 8: LDM_REQUIRE(win && a.Wq % 64 == 0, "dec1 (variant 3): 64-column rows");
+                if (guided) return step_dec1_guided(0, a, s, st);
+                LDM_REQUIRE(s.xs && s.coef, "dec1 (variant 3): sampler state");
                 if (s.msolver) return launch<0, 64, 32, 1, 2, 2, 4, 9, 9, EPI_MSOLVER | EPI_WINDOW, 1>(a, s.dtype, st);
                 return launch<0, 64, 32, 1, 2, 2, 4, 9, 9, EPI_DDIM | EPI_WINDOW, 1>(a, s.dtype, st);
             case 3: LDM_REQUIRE(s.y && a.Hin == 4 && a.Win == 16 && plane_taps(), "enc4 (variant 3): y, 4 x 16 input plane");
@@ -1268,7 +1325,16 @@ int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st)
             if (window_taps() && a.Wq % 32 == 0)
                 return launch<2, 128, 64, 1, 2, 1, 4, 18, 18, EPI_RELU | EPI_SKIP | EPI_WINDOW>(a, s.dtype, st);
             return launch<2, 128, 64, 1, 2, 1, 4, 18, 18, EPI_RELU | EPI_SKIP>(a, s.dtype, st);
-        default: LDM_REQUIRE(s.xs && s.coef, "dec1: sampler state, coefficients");
+        default:
+            if (guided) {   // the same four geometries
+                if (dec1_thin(W)) {
+                    if (window_taps()) return step_dec1_guided(1, a, s, st);
+                    return step_dec1_guided(2, a, s, st);
+                }
+                if (window_taps() && a.Wq % 32 == 0) return step_dec1_guided(3, a, s, st);
+                return step_dec1_guided(4, a, s, st);
+            }
+            LDM_REQUIRE(s.xs && s.coef, "dec1: sampler state, coefficients");
             if (s.msolver) {   // the same four geometries with the multistep epilogue
                 if (dec1_thin(W)) {
                     if (window_taps()) return launch<0, 64, 32, 1, 2, 2, 2, 18, 18, EPI_MSOLVER | EPI_WINDOW>(a, s.dtype, st);
@@ -1417,3 +1483,4 @@ extern "C" int ldm_step_conv_dt(int32_t layer, int32_t B, int32_t H, int32_t W, 
     LDM_REQUIRE(layer != 8, "ldm_step_conv: dec1 runs fused with the DDIM update (ldm_ddim_sample)");
     return step_conv(layer, B, H, W, s, (hipStream_t)stream);
 }
+#endif   // UCONV_GUIDE_TU

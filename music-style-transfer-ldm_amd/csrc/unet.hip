@@ -98,6 +98,9 @@ struct UNetWs {
     float* xs;                      // the sampler state in NHWC (reverse loop with the step kernels)
     float* uks;                     // split-K counters + slabs of the K-split step kernels (uconv.hip)
     float *ubn, *p1;                // the bottleneck's folded values U and CA1's probabilities (bfold.hip)
+    // the guided loop (carved at twice the caller's batch): the base half's noise prediction, and the target and
+    // base style maps / key biases side by side as one doubled batch
+    float *eb, *s5cat, *s6cat, *kb5cat, *kb6cat;
     int64_t total;
 };
 
@@ -126,7 +129,8 @@ static bool use_bneck_fold(const ldm_unet_shape& s, const ldm_unet_weights* w) {
 
 // S5 / S6: key counts of CA2 / CA1 (style mixing: several references stacked along the keys); 0 = the map's own
 // token count, which is every caller but the *_mix loops.  Only the K/V projections and the folded keys scale.
-static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float* base, int64_t S5 = 0, int64_t S6 = 0) {
+static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float* base, int64_t S5 = 0, int64_t S6 = 0,
+                    bool guided = false) {
     const int64_t B = s.B, nf = s.nf, HW = (int64_t)s.H * s.W;
     const int64_t HW2 = HW / 4, L2 = HW / 16, L1 = HW / 64;
     if (S5 <= 0) S5 = L2;
@@ -166,6 +170,13 @@ static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float*
     const bool bfold = use_bneck_fold(s, wts) && S6 == L1;   // (its kernels are built for 16 keys)
     w.ubn = take(bfold ? B * 512 * 576 : 0);
     w.p1 = take(bfold ? B * 4 * L1 * L1 : 0);
+    if (guided) {   // (after everything else: the unguided carve is the one it always was)
+        w.eb = take(B / 2 * (int64_t)s.C * HW);
+        w.s5cat = take(B * 256 * S5);
+        w.s6cat = take(B * 512 * S6);
+        w.kb5cat = take(B * S5);
+        w.kb6cat = take(B * S6);
+    }
     w.total = off;
     return w;
 }
@@ -179,6 +190,12 @@ struct DdimFuse {
     float* eps_log;
     bool msolver;            // the multistep solver's update instead: coef is an 8-float row, eta unused, x0_log required
     const float* x0_prev;    // msolver: the previous step's x0 log or NULL (first-order step)
+    // style guidance: gB = the caller's batch (the body runs at 2 gB: targets, then bases), 0 = none.  dec1 then runs
+    // as two launches at gB: the base half as a plain conv into eb, the target half guided against it by gscale [gB],
+    // updating x's first half and storing the new state to its second half too (x is the doubled state).
+    int gB;
+    float* eb;
+    const float* gscale;
 };
 
 static int conv_call(const ldm_unet_shape& s, float* convws, int layer, const ldm_conv_plan& plan, const float* x, const float* w,
@@ -209,6 +226,41 @@ static int conv_call(const ldm_unet_shape& s, float* convws, int layer, const ld
         int _rc = (expr);        \
         if (_rc) return _rc;     \
     } while (0)
+
+// dec1 of conv.hip's loops: one launch with the fused update, or the guided loop's two at the caller's batch.  The
+// bound plan is the doubled batch's; the halves run the same kind, tile and K split (the pack and the per-element
+// summation order depend on nothing else), whose workspace need is no larger.
+static int dec1_call(const ldm_unet_shape& s, const ldm_unet_weights& w, const float* d2, float* convws, float* out,
+                     hipStream_t st, const DdimFuse* fuse) {
+    if (!fuse || !fuse->gB)
+        return conv_call(s, convws, 8, w.conv_plan[8], d2, w.conv_w[8], w.conv_b[8], LDM_ACT_NONE, nullptr, nullptr, out, st,
+                         fuse);
+    ldm_unet_shape sh = s;
+    sh.B = fuse->gB;
+    ldm_conv_desc d;
+    LDM_TRY(layer_desc(sh, 8, d));
+    const ldm_conv_plan& bound = w.conv_plan[8];
+    LDM_REQUIRE(bound.kind >= 0 && bound.kind <= 2, "guided loop: dec1's plan must be a direct or fp32 MFMA plan");
+    ldm_conv_plan plan;
+    LDM_TRY(ldm_conv_make_plan_forced(&d, bound.kind, bound.tm, bound.tn, bound.wk, bound.balance ? -bound.ks : bound.ks, &plan));
+    LDM_REQUIRE(plan.packed_floats == bound.packed_floats && plan.ws_floats <= bound.ws_floats, "guided loop: dec1 plan mismatch");
+    const int64_t HW = (int64_t)s.H * s.W;
+    EpiArgs eb{};
+    eb.bias = w.conv_b[8];
+    eb.act = LDM_ACT_NONE;
+    LDM_TRY(conv_forward_ex(d, plan, d2 + fuse->gB * HW * s.nf, w.conv_w[8], eb, fuse->eb, convws, st));
+    EpiArgs ep = eb;
+    if (fuse->msolver) ep.ms_coef = fuse->coef, ep.ms_x0_prev = fuse->x0_prev;
+    else ep.ddim_coef = fuse->coef;
+    ep.ddim_eta = fuse->eta;
+    ep.ddim_x = fuse->x;
+    ep.ddim_x0_log = fuse->x0_log;
+    ep.ddim_eps_log = fuse->eps_log;
+    ep.guide_eb = fuse->eb;
+    ep.guide_scale = fuse->gscale;
+    ep.ddim_x2 = fuse->x + fuse->gB * HW * s.C;
+    return conv_forward_ex(d, plan, d2, w.conv_w[8], ep, nullptr, convws, st);
+}
 
 // K/V projections of the style maps (the key/value half of both cross-attentions' in_proj,
 // model.py:153).  They depend only on s5 / s6, which are fixed for a whole reverse loop.
@@ -272,8 +324,7 @@ static int unet_forward(const ldm_unet_shape& s, const ldm_unet_weights& w, cons
     LDM_TRY(conv_call(s, ws.convws, 5, w.conv_plan[5], ws.zb, w.conv_w[5], w.conv_b[5], LDM_ACT_RELU, nullptr, ws.z3, ws.d4, st));
     LDM_TRY(conv_call(s, ws.convws, 6, w.conv_plan[6], ws.d4, w.conv_w[6], w.conv_b[6], LDM_ACT_RELU, nullptr, ws.z2, ws.d3, st));
     LDM_TRY(conv_call(s, ws.convws, 7, w.conv_plan[7], ws.d3, w.conv_w[7], w.conv_b[7], LDM_ACT_RELU, nullptr, ws.z1, ws.d2, st));
-    LDM_TRY(conv_call(s, ws.convws, 8, w.conv_plan[8], ws.d2, w.conv_w[8], w.conv_b[8], LDM_ACT_NONE, nullptr, nullptr, out, st,
-                      fuse));
+    LDM_TRY(dec1_call(s, w, ws.d2, ws.convws, out, st, fuse));
     return 0;
 }
 
@@ -299,8 +350,7 @@ static int unet_forward_folded(const ldm_unet_shape& s, const ldm_unet_weights& 
     LDM_TRY(conv_call(s, ws.convws, 5, w.conv_plan[5], ws.zb, w.conv_w[5], w.conv_b[5], LDM_ACT_RELU, nullptr, ws.z3, ws.d4, st));
     LDM_TRY(conv_call(s, ws.convws, 6, w.conv_plan[6], ws.d4, w.conv_w[6], w.conv_b[6], LDM_ACT_RELU, nullptr, ws.z2, ws.d3, st));
     LDM_TRY(conv_call(s, ws.convws, 7, w.conv_plan[7], ws.d3, w.conv_w[7], w.conv_b[7], LDM_ACT_RELU, nullptr, ws.z1, ws.d2, st));
-    LDM_TRY(conv_call(s, ws.convws, 8, w.conv_plan[8], ws.d2, w.conv_w[8], w.conv_b[8], LDM_ACT_NONE, nullptr, nullptr, nullptr,
-                      st, fuse));
+    LDM_TRY(dec1_call(s, w, ws.d2, ws.convws, nullptr, st, fuse));
     return 0;
 }
 
@@ -335,8 +385,25 @@ static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w,
     c[8].eps_log = fuse.eps_log;
     c[8].msolver = fuse.msolver;
     c[8].x0_prev = fuse.x0_prev;
+    auto dec1_guided = [&]() -> int {   // the base half into eb, then the target half guided against it
+        const int Bh = fuse.gB;
+        StepConv cb = c[8];
+        cb.x = ws.d2 + (size_t)Bh * HW * s.nf;
+        cb.y = fuse.eb;
+        cb.plain = 1;
+        cb.coef = nullptr, cb.xs = nullptr, cb.x0_log = nullptr, cb.eps_log = nullptr, cb.msolver = 0, cb.x0_prev = nullptr;
+        LDM_TRY(step_conv(8, Bh, s.H, s.W, cb, st));
+        StepConv ct = c[8];
+        ct.guide_eb = fuse.eb;
+        ct.guide_scale = fuse.gscale;
+        ct.xs2 = ws.xs + (size_t)Bh * HW * s.C;
+        return step_conv(8, Bh, s.H, s.W, ct, st);
+    };
     auto run = [&](int l0, int l1) -> int {   // layers [l0, l1]
-        for (int l = l0; l <= l1; ++l) LDM_TRY(step_conv(l, s.B, s.H, s.W, c[l], st));
+        for (int l = l0; l <= l1; ++l) {
+            if (l == 8 && fuse.gB) LDM_TRY(dec1_guided());
+            else LDM_TRY(step_conv(l, s.B, s.H, s.W, c[l], st));
+        }
         return 0;
     };
     LDM_TRY(run(0, 2));
@@ -401,28 +468,75 @@ extern "C" int ldm_unet_forward(const ldm_unet_shape* s, const ldm_unet_weights*
 // sample, the K/V projections and the key fold run over them, the bias goes into the folded keys' bias, and the
 // two attention launches of each step stream the keys (stylemix.hip).  With the maps' own counts and no bias every
 // call below is the one it always was.
-static int sample_loop(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
+// Style guidance (the *_guided entries, g != NULL): every step evaluates the denoiser under the target and under a
+// base style and steps on eps = e_b + scale (e_t - e_b) (guide_eps).  The body runs at twice the caller's batch,
+// samples [0, B) under the target maps and [B, 2B) under the base maps, on a doubled sampler state whose halves
+// stay bitwise equal; w holds the doubled batch's plans.  Only dec1 differs (dec1_call / unet_step_kernels).
+struct Guide {
+    const float *s5_base, *s6_base, *key_bias5_base, *key_bias6_base, *scale;
+};
+
+// out[r] = a[r] ++ b[r] for rows of rowlen floats (NULL a / b: zeros): the doubled batch's operands, once per loop
+__global__ __launch_bounds__(256) void concat_halves_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                            float* __restrict__ out, int64_t rowlen, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // over out
+    if (i >= n) return;
+    const int64_t r = i / (2 * rowlen), j = i - r * 2 * rowlen;
+    const float* src = j < rowlen ? a : b;
+    out[i] = src ? src[r * rowlen + (j < rowlen ? j : j - rowlen)] : 0.f;
+}
+static int concat_halves(const float* a, const float* b, float* out, int64_t rows, int64_t rowlen, hipStream_t st) {
+    const int64_t n = rows * 2 * rowlen;
+    hipLaunchKernelGGL(concat_halves_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, b, out, rowlen, n);
+    LDM_CHECK_LAUNCH("concat_halves_kernel");
+    return 0;
+}
+
+static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
                        const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta, float* x0_logs,
                        float* eps_logs, int64_t log_step_stride, float* workspace, void* stream, bool msolver,
                        int32_t S5 = 0, int32_t S6 = 0, const float* key_bias5 = nullptr,
-                       const float* key_bias6 = nullptr) {
+                       const float* key_bias6 = nullptr, const Guide* g = nullptr) {
+    ldm_unet_shape sh = *sc;   // the shape the body runs at
+    if (g) sh.B = 2 * sc->B;
+    const ldm_unet_shape* s = &sh;
     const int L2 = s->H * s->W / 16, L1 = s->H * s->W / 64;
     if (S5 <= 0) S5 = L2;
     if (S6 <= 0) S6 = L1;
-    const bool mix = S5 != L2 || S6 != L1 || key_bias5 || key_bias6;
+    const bool gbias = g && (key_bias5 || key_bias6 || g->key_bias5_base || g->key_bias6_base);
+    const bool mix = S5 != L2 || S6 != L1 || key_bias5 || key_bias6 || gbias;
     LDM_REQUIRE(!mix || w->use_fold, "style mix: the reverse loop attends over several references only with the "
                                      "folded cross-attentions (use_fold)");
-    UNetWs ws = carve(*s, w, workspace, S5, S6);
-    float* temb_all = workspace + ws.total;   // [nsteps*B, 128] (ldm_ddim_workspace_floats)
-    const int64_t dense = (int64_t)s->B * s->C * s->H * s->W;
+    UNetWs ws = carve(*s, w, workspace, S5, S6, g != nullptr);
+    float* temb_all = workspace + ws.total;   // [nsteps*B, 128] (ldm_ddim_workspace_floats[_guided])
+    const int64_t dense = (int64_t)sc->B * s->C * s->H * s->W;   // one step of the logs: the caller's batch
     LDM_REQUIRE(log_step_stride == 0 || log_step_stride >= dense, "ddim_sample: log stride smaller than a step");
     const int64_t n = log_step_stride ? log_step_stride : dense;
     hipStream_t st = (hipStream_t)stream;
     const size_t cw = msolver ? 8 : 4;   // floats per coefficient row
     // The time MLP depends only on t: all nsteps*B embeddings in one launch before the loop (the same
     // evaluations the reference makes one step at a time, model.py:203).
-    LDM_TRY(ldm_time_mlp_forward(t_table, 0, nsteps * s->B, 128, w->t_freqs, w->t_w1, w->t_b1, w->t_w2, w->t_b2,
-                                 temb_all, st));
+    if (g) {   // both halves share t: the caller's [nsteps, B] rows, each repeated for the base half
+        float* temb_b = temb_all + (size_t)nsteps * s->B * 128;
+        LDM_TRY(ldm_time_mlp_forward(t_table, 0, nsteps * sc->B, 128, w->t_freqs, w->t_w1, w->t_b1, w->t_w2, w->t_b2,
+                                     temb_b, st));
+        LDM_TRY(concat_halves(temb_b, temb_b, temb_all, nsteps, (int64_t)sc->B * 128, st));
+        // the doubled batch's style maps and key biases: targets, then bases
+        LDM_TRY(concat_halves(s5, g->s5_base, ws.s5cat, 1, (int64_t)sc->B * 256 * S5, st));
+        LDM_TRY(concat_halves(s6, g->s6_base, ws.s6cat, 1, (int64_t)sc->B * 512 * S6, st));
+        s5 = ws.s5cat, s6 = ws.s6cat;
+        if (key_bias5 || g->key_bias5_base) {
+            LDM_TRY(concat_halves(key_bias5, g->key_bias5_base, ws.kb5cat, 1, (int64_t)sc->B * S5, st));
+            key_bias5 = ws.kb5cat;
+        }
+        if (key_bias6 || g->key_bias6_base) {
+            LDM_TRY(concat_halves(key_bias6, g->key_bias6_base, ws.kb6cat, 1, (int64_t)sc->B * S6, st));
+            key_bias6 = ws.kb6cat;
+        }
+    } else {
+        LDM_TRY(ldm_time_mlp_forward(t_table, 0, nsteps * s->B, 128, w->t_freqs, w->t_w1, w->t_b1, w->t_w2, w->t_b2,
+                                     temb_all, st));
+    }
     // Likewise the style maps' K/V projections (model.py:153 with kv = s5 / s6, fixed for the loop).
     if (S5 == L2 && S6 == L1) {
         LDM_TRY(style_kv(*s, *w, s5, s6, ws, st));
@@ -431,6 +545,13 @@ static int sample_loop(const ldm_unet_shape* s, const ldm_unet_weights* w, float
         LDM_TRY(style_kv_tokens(*s, *w, 1, s6, S6, ws.kv1, st));
     }
     const int HW = s->H * s->W;
+    auto make_fuse = [&](int i, float* xstate) {
+        DdimFuse fuse{coef_table + cw * (size_t)i, eta, xstate, x0_logs ? x0_logs + (size_t)i * n : nullptr,
+                      eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
+                      msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
+        if (g) fuse.gB = sc->B, fuse.eb = ws.eb, fuse.gscale = g->scale;
+        return fuse;
+    };
     if (w->use_fold) {
         LDM_REQUIRE(w->ca_wq_raw[0] && w->ca_wq_raw[1] && w->fold_w[0] && w->fold_w[1] && w->fold_pb[0] && w->fold_pb[1],
                     "ddim_sample: use_fold needs the folded weights");
@@ -446,33 +567,33 @@ static int sample_loop(const ldm_unet_shape* s, const ldm_unet_weights* w, float
             // the bottleneck's value fold is built for CA1's own 16 keys without a bias: a mix leaves it
             const bool bfold = use_bneck_fold(*s, w) && S6 == L1 && !key_bias6;
             if (bfold) LDM_TRY(bneck_fold_values(w->step_bneck_w, ws.kv1, ws.ubn, s->B, st));
-            LDM_TRY(step_layout(x, ws.xs, s->B, s->C, HW, true, st));
+            LDM_TRY(step_layout(x, ws.xs, sc->B, s->C, HW, true, st));
+            if (g) LDM_TRY(step_layout(x, ws.xs + dense, sc->B, s->C, HW, true, st));
             for (int i = 0; i < nsteps; ++i) {
-                DdimFuse fuse{coef_table + cw * (size_t)i, eta, ws.xs, x0_logs ? x0_logs + (size_t)i * n : nullptr,
-                              eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
-                              msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
+                const DdimFuse fuse = make_fuse(i, ws.xs);
                 LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold));
             }
-            return step_layout(ws.xs, x, s->B, s->C, HW, false, st);
+            return step_layout(ws.xs, x, sc->B, s->C, HW, false, st);
         }
-        for (int i = 0; i < nsteps; ++i) {
-            DdimFuse fuse{coef_table + cw * (size_t)i, eta, x, x0_logs ? x0_logs + (size_t)i * n : nullptr,
-                          eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
-                          msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
-            LDM_TRY(unet_forward_folded(*s, *w, x, ws, st, temb_all + (size_t)i * s->B * 128, &fuse, S5, S6));
-        }
-        return 0;
+    }
+    // conv.hip's loops keep the state NCHW: in place on x, or when guided on the doubled state in the workspace
+    float* xstate = x;
+    if (g) {
+        LDM_TRY(concat_halves(x, x, ws.xs, 1, dense, st));
+        xstate = ws.xs;
     }
     for (int i = 0; i < nsteps; ++i) {
         // noise_pred = unet(x, t, style_embedding)                                (model.py:439)
         // and, fused into dec1's epilogue, the x0 / direction / eta update and the two log clones
         // (model.py:442-463) — bitwise the same fp32 op sequence as ldm_ddim_step.
-        DdimFuse fuse{coef_table + cw * (size_t)i, eta, x, x0_logs ? x0_logs + (size_t)i * n : nullptr,
-                      eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
-                      msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
-        LDM_TRY(unet_forward(*s, *w, x, t_table + (size_t)i * s->B, 0, s5, s6, nullptr, ws, st,
-                             temb_all + (size_t)i * s->B * 128, &fuse, /*kv_ready=*/true));
+        const DdimFuse fuse = make_fuse(i, xstate);
+        if (w->use_fold)
+            LDM_TRY(unet_forward_folded(*s, *w, xstate, ws, st, temb_all + (size_t)i * s->B * 128, &fuse, S5, S6));
+        else
+            LDM_TRY(unet_forward(*s, *w, xstate, t_table + (size_t)i * sc->B, 0, s5, s6, nullptr, ws, st,
+                                 temb_all + (size_t)i * s->B * 128, &fuse, /*kv_ready=*/true));
     }
+    if (g) LDM_HIP_TRY(hipMemcpyAsync(x, ws.xs, (size_t)dense * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
@@ -541,4 +662,86 @@ extern "C" int ldm_msolver_sample_mix(const ldm_unet_shape* s, const ldm_unet_we
     if (nsteps == 0) return 0;
     return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs, log_step_stride, workspace,
                        stream, true, S5, S6, key_bias5, key_bias6);
+}
+
+// ---- style guidance: the same loops under a target and a base style (sample_loop's Guide) -----------------------
+extern "C" int64_t ldm_ddim_workspace_floats_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps,
+                                                    int32_t S5, int32_t S6);
+
+// The entries take no buffer size, and the guided workspace is more than twice the unguided one: a buffer sized by
+// ldm_ddim_workspace_floats would be written past its end.  Before anything is launched the extent of the device
+// allocation that holds `workspace` is asked of the runtime and compared with the guided size.  This is exact for a
+// buffer that is an allocation of its own; a buffer carved from a larger pool is only known to end inside the pool.
+// Skipped under stream capture (a captured loop is run eagerly first) and where the runtime does not know the pointer.
+static int guided_workspace_ok(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5, int32_t S6,
+                               const float* workspace, void* stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (cs != hipStreamCaptureStatusNone) return 0;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)workspace) != hipSuccess || !base) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    const int64_t need = ldm_ddim_workspace_floats_guided(s, w, nsteps, S5, S6);
+    LDM_REQUIRE(need > 0, "guided sample: bad shape for the workspace size");
+    const int64_t avail = (int64_t)(((const char*)base + size) - (const char*)workspace);
+    LDM_REQUIRE(avail >= need * 4, "guided sample: the workspace's allocation ends before the size "
+                                   "ldm_ddim_workspace_floats_guided gives (was it sized by ldm_ddim_workspace_floats?)");
+    return 0;
+}
+
+static int guided_args_ok(const ldm_unet_shape* s, const float* s5_base, const float* s6_base, const float* guide_scale,
+                          int32_t S5, int32_t S6) {
+    LDM_REQUIRE(s5_base && s6_base, "guided sample: null base style maps");
+    LDM_REQUIRE(guide_scale, "guided sample: null guidance scale");
+    LDM_REQUIRE(S5 >= 0 && S6 >= 0, "guided sample: negative key count");
+    LDM_REQUIRE(s->B > 0 && s->B <= (1 << 20), "guided sample: bad batch");
+    return 0;
+}
+
+extern "C" int64_t ldm_ddim_workspace_floats_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps,
+                                                    int32_t S5, int32_t S6) {
+    if (!s || nsteps < 0 || S5 < 0 || S6 < 0 || s->B <= 0) return -1;
+    ldm_unet_shape sh = *s;
+    sh.B = 2 * s->B;
+    return carve(sh, w, nullptr, S5, S6, true).total + (int64_t)nsteps * 3 * s->B * 128;
+}
+
+extern "C" int ldm_ddim_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                                      const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
+                                      const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
+                                      const float* key_bias6_base, const float* guide_scale, const int64_t* t_table,
+                                      const float* coef_table, int32_t nsteps, float eta, float* x0_logs, float* eps_logs,
+                                      int64_t log_step_stride, float* workspace, void* stream) {
+    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace, "ddim_sample_guided: null argument");
+    LDM_REQUIRE(nsteps >= 0, "ddim_sample_guided: negative step count");
+    LDM_TRY(guided_args_ok(s, s5_base, s6_base, guide_scale, S5, S6));
+    if (nsteps == 0) return 0;
+    LDM_TRY(guided_workspace_ok(s, w, nsteps, S5, S6, workspace, stream));
+    const Guide g{s5_base, s6_base, key_bias5_base, key_bias6_base, guide_scale};
+    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, eta, x0_logs, eps_logs, log_step_stride, workspace,
+                       stream, false, S5, S6, key_bias5, key_bias6, &g);
+}
+
+extern "C" int ldm_msolver_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                                         const float* s6, const float* s5_base, const float* s6_base, int32_t S5,
+                                         int32_t S6, const float* key_bias5, const float* key_bias6,
+                                         const float* key_bias5_base, const float* key_bias6_base,
+                                         const float* guide_scale, const int64_t* t_table, const float* coef_table,
+                                         int32_t nsteps, float* x0_logs, float* eps_logs, int64_t log_step_stride,
+                                         float* workspace, void* stream) {
+    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace && x0_logs,
+                "msolver_sample_guided: null argument");
+    LDM_REQUIRE(nsteps >= 0, "msolver_sample_guided: negative step count");
+    LDM_TRY(guided_args_ok(s, s5_base, s6_base, guide_scale, S5, S6));
+    if (nsteps == 0) return 0;
+    LDM_TRY(guided_workspace_ok(s, w, nsteps, S5, S6, workspace, stream));
+    const Guide g{s5_base, s6_base, key_bias5_base, key_bias6_base, guide_scale};
+    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs, log_step_stride, workspace,
+                       stream, true, S5, S6, key_bias5, key_bias6, &g);
 }

@@ -214,6 +214,16 @@ SIGNATURES = {
     "ldm_msolver_sample_mix": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
                                          c_int32, c_int32, c_fp, c_fp, c_vp, c_fp, c_int32, c_fp, c_fp, c_int64, c_fp,
                                          c_vp]),
+    # style guidance: target and base maps, their key biases, a per-sample scale
+    "ldm_ddim_workspace_floats_guided": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_int32,
+                                                   c_int32, c_int32]),
+    "ldm_ddim_sample_guided": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
+                                         c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_vp, c_fp,
+                                         c_int32, c_float, c_fp, c_fp, c_int64, c_fp, c_vp]),
+    "ldm_msolver_sample_guided": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
+                                            c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_vp, c_fp,
+                                            c_int32, c_fp, c_fp, c_int64, c_fp, c_vp]),
+    "ldm_guide_eps": (c_int32, [c_fp, c_fp, c_fp, c_int64, c_int32, c_fp, c_vp]),
     # backward / optimiser
     "ldm_conv_tiled_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),
     "ldm_conv_sconv_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),

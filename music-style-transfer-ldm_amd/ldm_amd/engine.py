@@ -194,10 +194,25 @@ class UNetEngine:
         self._bound[skey] = (vkey, w)
         return w
 
-    def workspace(self, shape, device, nsteps=0, slot=0, keys=None):
+    def workspace(self, shape, device, nsteps=0, slot=0, keys=None, guided=False, plan_batch=None):
         """Workspace for this shape and its bound plans; `slot` separates concurrently running sub-batch
         chains.  Zero-filled on allocation: it carries the split-K tile counters (ldm_capi.h).
-        keys = (S5, S6): the style-mixing loops' workspace for those key counts (a buffer of its own)."""
+        keys = (S5, S6): the style-mixing loops' workspace for those key counts (a buffer of its own).
+        guided: the guided loops' workspace for the caller's `shape` (sized by the guided function for the doubled
+        batch the body runs at; a buffer of its own; keys (0, 0) = the maps' own counts; plan_batch as in
+        _guided_weights)."""
+        if guided:
+            w = self._guided_weights(shape.B, shape.C, shape.H, shape.W, plan_batch)
+            keys = tuple(keys) if keys else (0, 0)
+            n = L.load().ldm_ddim_workspace_floats_guided(byref(shape), byref(w), int(nsteps), int(keys[0]), int(keys[1]))
+            if n <= 0:
+                raise RuntimeError("ldm_ddim_workspace_floats_guided failed")
+            key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot, "guided", plan_batch or 0) + keys
+            ws = self._ws.get(key)
+            if ws is None or ws.numel() < n:
+                ws = torch.zeros(int(n), device=device, dtype=torch.float32)
+                self._ws[key] = ws
+            return ws
         w = self.weights(shape)
         if keys is None:
             n = L.load().ldm_ddim_workspace_floats(byref(shape), byref(w), int(nsteps))
@@ -270,7 +285,7 @@ class UNetEngine:
     def _mix_check(self, x, s5, s6, key_bias5, key_bias6):
         """Validates a style mix's operands and returns (S5, S6, bias pointers); raises where no mixing path exists."""
         B, C, H, W = x.shape
-        S5, S6 = self.mix_keys(x, s5, s6, key_bias5, key_bias6)
+        S5, S6 = s5.shape[2] * s5.shape[3], s6.shape[2] * s6.shape[3]   # (= mix_keys where that is not None)
         L2, L1 = (H // 4) * (W // 4), (H // 8) * (W // 8)
         if tuple(s5.shape[:2]) != (B, 256) or tuple(s6.shape[:2]) != (B, 512) or S5 % L2 or S6 % L1 or \
                 S5 // L2 != S6 // L1 or s5.shape[3] != W // 4 or s6.shape[3] != W // 8:
@@ -291,8 +306,92 @@ class UNetEngine:
             ptrs.append(kb.data_ptr())
         return S5, S6, ptrs[0], ptrs[1]
 
+    @staticmethod
+    def guidance_scale(scale, B, device=None):
+        """The per-sample guidance strengths as a contiguous fp32 [B] tensor (on `device` when given): a Python
+        number is broadcast, a tensor must hold B entries.  Finite values only (negative allowed): ValueError
+        otherwise."""
+        if isinstance(scale, torch.Tensor):
+            t = scale.detach().to(torch.float32).reshape(-1)
+            if t.numel() == 1 and B != 1:
+                t = t.expand(B)
+            if t.numel() != B:
+                raise ValueError(f"guidance_scale: need one strength per sample ([{B}]), got {tuple(scale.shape)}")
+        else:
+            v = float(scale)
+            t = torch.full((B,), v, dtype=torch.float32)
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("guidance_scale must be finite (NaN / inf given)")
+        t = t.contiguous()
+        return t.to(device) if device is not None else t
+
+    @staticmethod
+    def is_unguided(base, guidance_scale):
+        """True where the arguments select today's samplers: no base and a scale of exactly 1 (every entry)."""
+        if base is not None:
+            return False
+        if isinstance(guidance_scale, torch.Tensor):
+            return bool((guidance_scale.detach() == 1).all())
+        return float(guidance_scale) == 1.0
+
+    def _guided_keys(self, x, s5, s6, key_bias5, key_bias6, base):
+        """(S5, S6) of a guided loop: the key counts where either side is a mix (stacked maps or a bias), else (0, 0)."""
+        if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is None and base[2] is None and base[3] is None:
+            return 0, 0
+        return s5.shape[2] * s5.shape[3], s6.shape[2] * s6.shape[3]
+
+    def _guided_weights(self, B, C, H, W, plan_batch=None):
+        """The weights a guided loop of caller batch B binds: those of the doubled batch 2B the body runs at.
+        plan_batch (a sub-batch chain of a split loop: the whole loop's batch): the chain runs the plans chosen for the
+        whole loop's doubled batch instead of its own, so that a sample's arithmetic does not depend on how the batch
+        is split (ldm_conv_make_plan picks the K/V projections' kernel kind and K split by the column count).  Only on
+        the step-kernel path, whose sole planned launches are those two projections, and only where their plans need
+        no split-K workspace (its size is per batch); otherwise the chain's own plans, as for the unguided loops."""
+        if plan_batch and plan_batch != B:
+            wf = self.weights(self.shape(2 * plan_batch, C, H, W))
+            if wf.use_step and wf.ca_plan_kv[0].ws_floats == 0 and wf.ca_plan_kv[1].ws_floats == 0:
+                return wf
+        return self.weights(self.shape(2 * B, C, H, W))
+
+    def _guided_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5,
+                     key_bias6, base, scale, plan_batch=None):
+        """One guided C loop (ldm_*_sample_guided): base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the
+        target's key counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights."""
+        B, C, H, W = x.shape
+        shape = self.shape(B, C, H, W)
+        n = t_table.shape[0]
+        s5b, s6b, kb5b, kb6b = base
+        ops.require_device(s5b, s6b, scale, what="guidance operand")
+        if tuple(s5b.shape) != tuple(s5.shape) or tuple(s6b.shape) != tuple(s6.shape):
+            raise ValueError(f"guidance: the base style maps must have the target's shapes (same key counts): target "
+                             f"{tuple(s5.shape)}, {tuple(s6.shape)}; base {tuple(s5b.shape)}, {tuple(s6b.shape)} "
+                             "(LDM.tile_embedding repeats a single style for a mix of R references)")
+        if scale.dtype != torch.float32 or tuple(scale.shape) != (B,) or not scale.is_contiguous():
+            raise ValueError(f"guidance: scale must be a contiguous fp32 [{B}] device tensor, got {scale.dtype} "
+                             f"{tuple(scale.shape)}")
+        S5, S6 = self._guided_keys(x, s5, s6, key_bias5, key_bias6, base)
+        p5 = p6 = p5b = p6b = None
+        if S5:
+            S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
+            _, _, p5b, p6b = self._mix_check(x, s5b, s6b, kb5b, kb6b)
+        elif tuple(s5.shape) != (B, 256, H // 4, W // 4) or tuple(s6.shape) != (B, 512, H // 8, W // 8):
+            raise RuntimeError(f"UNet: style maps must be s5 [B,256,H/4,W/4], s6 [B,512,H/8,W/8] for z {tuple(x.shape)}; "
+                               f"got {tuple(s5.shape)}, {tuple(s6.shape)}")
+        w = self._guided_weights(B, C, H, W, plan_batch)   # the body runs at the doubled batch: targets, then bases
+        ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6), guided=True, plan_batch=plan_batch)
+        head = (byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(), s5b.data_ptr(), s6b.data_ptr(), S5, S6,
+                p5, p6, p5b, p6b, scale.data_ptr(), t_table.data_ptr(), coef_table.data_ptr(), n)
+        tail = (ops._p(eps_logs), int(log_stride), ws.data_ptr(), ops.stream_handle())
+        if solver == "msolver":
+            L.call("ldm_msolver_sample_guided", *head, x0_logs.data_ptr(), *tail)
+        else:
+            L.call("ldm_ddim_sample_guided", *head, float(eta), ops._p(x0_logs), *tail)
+
     def _ddim_call(self, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5=None,
-                   key_bias6=None):
+                   key_bias6=None, base=None, scale=None, plan_batch=None):
+        if base is not None:
+            return self._guided_call("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
+                                     key_bias5, key_bias6, base, scale, plan_batch)
         B, C, H, W = x.shape
         shape = self.shape(B, C, H, W)
         n = t_table.shape[0]
@@ -311,7 +410,10 @@ class UNetEngine:
                int(log_stride), ws.data_ptr(), ops.stream_handle())
 
     def _msolver_call(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs, log_stride, slot, key_bias5=None,
-                      key_bias6=None):
+                      key_bias6=None, base=None, scale=None, plan_batch=None):
+        if base is not None:
+            return self._guided_call("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, log_stride, slot,
+                                     key_bias5, key_bias6, base, scale, plan_batch)
         B, C, H, W = x.shape
         shape = self.shape(B, C, H, W)
         n = t_table.shape[0]
@@ -330,22 +432,22 @@ class UNetEngine:
                ws.data_ptr(), ops.stream_handle())
 
     def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None, key_bias5=None,
-                     key_bias6=None):
+                     key_bias6=None, base=None, guidance_scale=1.0):
         """ddim_loop's twin for the multistep solver (DPM-Solver++(2M) or its first-order form): coef_table
         [n,8] from ForwardDiffusion.multistep_coefs (device), no eta.  x0_logs [n,B,C,H,W] is required: step i
-        reads step i-1's slot as its history.  Same sub-batch chains as ddim_loop."""
+        reads step i-1's slot as its history.  Same sub-batch chains, base= and guidance_scale= as ddim_loop."""
         if x0_logs is None:
             raise ValueError("msolver_loop: x0_logs is required (it is the solver's history)")
         if coef_table.dim() != 2 or coef_table.shape[1] != 8 or coef_table.shape[0] != t_table.shape[0]:
             raise ValueError(f"msolver_loop: coef_table must be [n,8] for n = {t_table.shape[0]} steps, "
                              f"got {tuple(coef_table.shape)}")
         return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
-                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None:
-                          self._msolver_call(xs, a5, a6, t, coef_table, x0l, epl, stride, slot, b5, b6),
-                          key_bias5, key_bias6)
+                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None, base=None, scale=None, pb=None:
+                          self._msolver_call(xs, a5, a6, t, coef_table, x0l, epl, stride, slot, b5, b6, base, scale, pb),
+                          key_bias5, key_bias6, base, guidance_scale)
 
     def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None,
-                  key_bias5=None, key_bias6=None):
+                  key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0):
         """In-place reverse loop on x ([B,C,H,W] contiguous fp32).  t_table [n,B] int64, coef [n,4] (device).
 
         Style mixing: s5 / s6 may hold R style references stacked along the map's height (s5 [B,256,R*H/4,W/4],
@@ -353,20 +455,32 @@ class UNetEngine:
         [B,R*H*W/64] (fp32, the log of each key's reference weight, -inf allowed; None = equal weights).  Needs the
         folded engine; the sub-batch split slices the biases with the maps.
 
+        Style guidance: base = (s5_base, s6_base, key_bias5_base, key_bias6_base) (maps shaped like the target's, the
+        biases None or as above) makes every step evaluate the denoiser under both styles and step on
+        e_b + guidance_scale * (e_t - e_b); guidance_scale is a float or a [B] tensor (finite).  With base=None the
+        call is the unguided one, argument for argument (a scale other than 1 then has nothing to guide against:
+        ValueError).
+
         split > 1 runs the batch as that many independent sub-batch chains, each on its own stream
         (forked from and joined back into the current stream, so it also works under graph capture).
         The path is per-sample, so the result is the same up to fp32 summation order (a sub-batch
         size may get a conv plan that splits K differently); the chains' launch and memory latencies
         overlap each other's work."""
         return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
-                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None:
-                          self._ddim_call(xs, a5, a6, t, coef_table, eta, x0l, epl, stride, slot, b5, b6),
-                          key_bias5, key_bias6)
+                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None, base=None, scale=None, pb=None:
+                          self._ddim_call(xs, a5, a6, t, coef_table, eta, x0l, epl, stride, slot, b5, b6, base, scale, pb),
+                          key_bias5, key_bias6, base, guidance_scale)
 
-    def _loop(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5=None, key_bias6=None):
+    def _loop(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5=None, key_bias6=None, base=None,
+              guidance_scale=1.0):
         """The whole batch in one C call, or one per sub-batch chain; call(x, s5, s6, t, x0_logs, eps_logs,
-        log_stride, slot[, key_bias5, key_bias6]) is one sampler's C call."""
+        log_stride, slot[, key_bias5, key_bias6[, base, scale]]) is one sampler's C call."""
         B = x.shape[0]
+        if base is not None:
+            return self._loop_guided(x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5, key_bias6,
+                                     base, guidance_scale)
+        if not self.is_unguided(None, guidance_scale):
+            raise ValueError("guidance_scale other than 1 needs a base style to guide against (base=)")
         keys = self.mix_keys(x, s5, s6, key_bias5, key_bias6)
         if keys is not None:
             self._mix_check(x, s5, s6, key_bias5, key_bias6)
@@ -405,14 +519,59 @@ class UNetEngine:
         return x
 
 
+    def _loop_guided(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5, key_bias6, base, scale):
+        """_loop for a guided sampler: the base maps, their biases and the scales are sliced with the batch.  On the
+        step-kernel path the sub-batch chains run the whole batch's plans (_guided_weights), so split > 1 gives each
+        sample bitwise what split = 1 gives it while both select the same per-batch forms (the bottleneck value
+        fold applies up to a doubled batch of 8)."""
+        B = x.shape[0]
+        if len(base) != 4:
+            raise ValueError("base must be (s5_base, s6_base, key_bias5_base, key_bias6_base)")
+        if not (isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and
+                tuple(scale.shape) == (B,) and scale.is_contiguous()):   # (a graph's static buffer is passed as it is)
+            scale = self.guidance_scale(scale, B, x.device)
+        base = (ops.f32c(base[0]), ops.f32c(base[1]), base[2], base[3])
+        if plan is None:
+            plan = self.split_plan(t_table, B, split) if split > 1 else None
+        if not plan or len(plan) == 1:
+            call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6, base, scale)
+            return x
+        per_step = x[0].numel() * B
+        main = torch.cuda.current_stream(x.device)
+        streams = self.side_streams(x.device, len(plan))
+        C, H, W = x.shape[1:]
+        keys = self._guided_keys(x, s5, s6, key_bias5, key_bias6, base)
+        for k, (lo, hi, t_sub) in enumerate(plan):   # bind / pack / allocate on the main stream first
+            self.workspace(self.shape(hi - lo, C, H, W), x.device, t_table.shape[0], k, keys=keys, guided=True,
+                           plan_batch=B)
+
+        def cut(v, lo, hi):
+            return None if v is None else v[lo:hi]
+
+        for k, (lo, hi, t_sub) in enumerate(plan):
+            st = streams[k]
+            st.wait_stream(main)
+            if not torch.cuda.is_current_stream_capturing():
+                t_sub.record_stream(st)
+            with torch.cuda.stream(st):
+                call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, None if x0_logs is None else x0_logs[0, lo:hi],
+                     None if eps_logs is None else eps_logs[0, lo:hi], per_step, k, cut(key_bias5, lo, hi),
+                     cut(key_bias6, lo, hi), tuple(cut(v, lo, hi) for v in base), scale[lo:hi], B)
+        for st in streams:
+            main.wait_stream(st)
+        return x
+
+
 class GraphedDDIM:
     """A captured reverse loop with static buffers: replay() re-runs all n steps from x_init."""
 
     def __init__(self, engine, x_init, s5, s6, t_table, coef_table, eta, logs=True, split=1, solver="ddim",
-                 key_bias5=None, key_bias6=None):
+                 key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0):
         """solver="ddim": coef_table [n,4] and eta, the reference's update; solver="msolver": coef_table [n,8]
         (ForwardDiffusion.multistep_coefs), eta unused and the x0 logs always kept (the solver's history).
-        s5 / s6 may be stacked style references with key_bias5 / key_bias6 (UNetEngine.ddim_loop)."""
+        s5 / s6 may be stacked style references with key_bias5 / key_bias6 (UNetEngine.ddim_loop).
+        base / guidance_scale: style guidance as in UNetEngine.ddim_loop; the strengths live in the static device
+        buffer `scale` ([B] fp32), which set_guidance_scale() rewrites between replays without a new capture."""
         if solver not in ("ddim", "msolver"):
             raise ValueError(f"GraphedDDIM: unknown solver {solver!r}")
         self.solver = solver
@@ -426,6 +585,12 @@ class GraphedDDIM:
         self.s6 = s6.contiguous().clone()
         self.kb5 = None if key_bias5 is None else key_bias5.contiguous().clone()
         self.kb6 = None if key_bias6 is None else key_bias6.contiguous().clone()
+        self.base = self.scale = None
+        if base is not None:
+            self.base = tuple(None if v is None else ops.f32c(v).clone() for v in base)
+            self.scale = engine.guidance_scale(guidance_scale, x_init.shape[0], dev)
+        elif not engine.is_unguided(None, guidance_scale):
+            raise ValueError("guidance_scale other than 1 needs a base style to guide against (base=)")
         self.t_table = t_table.to(dev).contiguous()
         self.coef = coef_table.to(dev).contiguous()
         n = self.t_table.shape[0]
@@ -459,21 +624,31 @@ class GraphedDDIM:
                 epl = None if self.eps_logs is None else self.eps_logs[0, lo:hi]
                 kb5 = None if self.kb5 is None else self.kb5[lo:hi]
                 kb6 = None if self.kb6 is None else self.kb6[lo:hi]
+                gb = None if self.base is None else tuple(None if v is None else v[lo:hi] for v in self.base)
+                gs = None if self.scale is None else self.scale[lo:hi]
                 if solver == "msolver":
                     engine._msolver_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, x0l, epl,
-                                         per_step, k, kb5, kb6)
+                                         per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None)
                 else:
                     engine._ddim_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
-                                      x0l, epl, per_step, k, kb5, kb6)
+                                      x0l, epl, per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None)
             self.graphs.append(g)
 
     def _run(self, plan=None):
+        guide = {} if self.base is None else {"base": self.base, "guidance_scale": self.scale}
         if self.solver == "msolver":
             self.engine.msolver_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.x0_logs, self.eps_logs,
-                                     plan=plan, key_bias5=self.kb5, key_bias6=self.kb6)
+                                     plan=plan, key_bias5=self.kb5, key_bias6=self.kb6, **guide)
         else:
             self.engine.ddim_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.eta, self.x0_logs,
-                                  self.eps_logs, plan=plan, key_bias5=self.kb5, key_bias6=self.kb6)
+                                  self.eps_logs, plan=plan, key_bias5=self.kb5, key_bias6=self.kb6, **guide)
+
+    def set_guidance_scale(self, guidance_scale):
+        """Writes new strengths (float or [B]) into the static buffer the captured loop reads: the next replay runs
+        at them.  Only for a graph captured with a base style."""
+        if self.scale is None:
+            raise ValueError("set_guidance_scale: this loop was captured without a base style")
+        self.scale.copy_(self.engine.guidance_scale(guidance_scale, self.scale.shape[0]), non_blocking=False)
 
     def replay(self):
         if self.streams is None:

@@ -988,6 +988,21 @@ def msolver_step_(x, eps, coef8, x0_log, x0_prev=None, eps_log=None):
     return x
 
 
+def guide_eps(e_t, e_b, scale, out=None):
+    """Style guidance on whole noise predictions (ldm_guide_eps): e_b + scale[b] * (e_t - e_b) per element in fp32,
+    one rounding per operation.  e_t / e_b [B, ...] contiguous fp32, scale a device fp32 [B] tensor."""
+    require_device(e_t, e_b, scale, out)
+    if e_t.shape != e_b.shape or scale.dtype != torch.float32 or tuple(scale.shape) != (e_t.shape[0],):
+        raise ValueError(f"guide_eps: e_t / e_b must share a shape and scale be fp32 [B]; got {tuple(e_t.shape)}, "
+                         f"{tuple(e_b.shape)}, {scale.dtype} {tuple(scale.shape)}")
+    e_t, e_b, scale = f32c(e_t), f32c(e_b), scale.contiguous()
+    out = torch.empty_like(e_t) if out is None else out
+    B = e_t.shape[0]
+    L.call("ldm_guide_eps", e_t.data_ptr(), e_b.data_ptr(), scale.data_ptr(), e_t.numel() // B, B, out.data_ptr(),
+           stream_handle())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # data formats either side of the path (dataio.hip): 8-bit mel PNG pixels <-> dB, ToTensor
 # ------------------------------------------------------------------------------------------------

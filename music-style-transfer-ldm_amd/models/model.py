@@ -420,9 +420,26 @@ class LDM(nn.Module):
         }
 
     # -------------------------------------------------------------------------------------------
-    def _reverse(self, z_t, style_embedding, times, eta, order=0):
+    def _reverse(self, z_t, style_embedding, times, eta, order=0, base_embedding=None, guidance_scale=1.0):
         """The shared body of the samplers: len(times)-1 UNet + update steps in one C call.  order 0: the
-        reference's DDIM-style update with eta; 1 / 2: the multistep solver of that order (eta unused)."""
+        reference's DDIM-style update with eta; 1 / 2: the multistep solver of that order (eta unused).
+
+        base_embedding / guidance_scale (a finite float or one per sample, [B]): style guidance.  Each step
+        evaluates the denoiser under both embeddings on the same x and t and steps on eps = e_b + s (e_t - e_b)
+        (fp32, one rounding per operation); the logs hold the guided x0 / eps.  Without a base and at scale 1 the
+        calls below are the unguided ones, argument for argument."""
+        guided = not UNetEngine.is_unguided(base_embedding, guidance_scale)
+        if guided:      # the checks, before anything runs
+            if base_embedding is None:
+                raise ValueError("guidance_scale other than 1 needs a base style to guide against (base_embedding=)")
+            scale = UNetEngine.guidance_scale(guidance_scale, z_t.shape[0])      # ValueError on NaN / inf / a wrong count
+            for k in ("s5", "s6"):
+                if tuple(base_embedding[k].shape) != tuple(style_embedding[k].shape):
+                    raise ValueError(
+                        f"guidance: the base embedding must have the target's key counts: target s5 "
+                        f"{tuple(style_embedding['s5'].shape)}, s6 {tuple(style_embedding['s6'].shape)}; base s5 "
+                        f"{tuple(base_embedding['s5'].shape)}, s6 {tuple(base_embedding['s6'].shape)} (tile_embedding "
+                        "repeats a single style for a mix of R references)")
         n = int(times.numel()) - 1
         logs = {"timesteps": [], "pred_x0": [], "noise_pred": []}
         if n <= 0:
@@ -442,14 +459,21 @@ class LDM(nn.Module):
         kb5, kb6 = style_embedding.get("key_bias5"), style_embedding.get("key_bias6")
         mix = UNetEngine.mix_keys(x, s5, s6, kb5, kb6) is not None   # several references (encode_styles)
         coefs = coefs.to(dev)
+        guide = {}
+        if guided:
+            base = (ops.f32c(base_embedding["s5"]), ops.f32c(base_embedding["s6"]), base_embedding.get("key_bias5"),
+                    base_embedding.get("key_bias6"))
+            scale = scale.to(dev)
+            mix = mix or base[2] is not None or base[3] is not None
+            guide = {"base": base, "guidance_scale": scale}
         with torch.no_grad():
-            if UNetEngine.supports(x.shape[1]) and mix:
+            if UNetEngine.supports(x.shape[1]) and (mix or guided):
                 eng = engine_for(self.unet)
                 if order:
-                    eng.msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs, key_bias5=kb5, key_bias6=kb6)
+                    eng.msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs, key_bias5=kb5, key_bias6=kb6, **guide)
                 else:
                     eng.ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs, key_bias5=kb5,
-                                  key_bias6=kb6)
+                                  key_bias6=kb6, **guide)
             elif UNetEngine.supports(x.shape[1]):
                 if order:
                     engine_for(self.unet).msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs)
@@ -460,8 +484,11 @@ class LDM(nn.Module):
                     raise RuntimeError(f"style mix: latent width {x.shape[1]} runs the per-layer path, which takes one "
                                        "style map per sample (the fused engine needs a multiple of 8, at least 16)")
                 emb = {"s5": s5, "s6": s6}
+                emb_b = {"s5": base[0], "s6": base[1]} if guided else None
                 for i in range(n):
                     eps = self.unet(x, t_table[i], emb)
+                    if guided:      # the second UNet call of the step, then the guidance kernel
+                        eps = ops.guide_eps(ops.f32c(eps), ops.f32c(self.unet(x, t_table[i], emb_b)), scale)
                     if order:
                         ops.msolver_step_(x, eps, coefs[i].contiguous(), x0_logs[i], x0_logs[i - 1] if i else None,
                                           eps_logs[i])
@@ -471,6 +498,21 @@ class LDM(nn.Module):
         logs["pred_x0"] = list(x0_logs.unbind(0))
         logs["noise_pred"] = list(eps_logs.unbind(0))
         return x, logs
+
+    @staticmethod
+    def tile_embedding(emb, R):
+        """A single-style embedding as R stacked copies of itself along the maps' height, without key biases: the base
+        of a guided sampler whose target is a mix of R references (R equally weighted copies of one style attend
+        like that style)."""
+        R = int(R)
+        if R < 1:
+            raise ValueError(f"tile_embedding: R must be at least 1, got {R}")
+        if emb.get("key_bias5") is not None or emb.get("key_bias6") is not None or int(emb.get("refs", 1)) != 1:
+            raise ValueError("tile_embedding: a single-style embedding is expected (no references, no key bias)")
+        out = {"refs": R, "key_bias5": None, "key_bias6": None}
+        for k in ("s5", "s6"):
+            out[k] = emb[k].repeat(1, 1, R, 1).contiguous() if R > 1 else emb[k]
+        return out
 
     MAX_STYLE_REFS = 8
 
@@ -578,21 +620,28 @@ class LDM(nn.Module):
                              f"{steps}, t_start {t_start} (with more steps than indices two times coincide)")
         return torch.linspace(t_start, 0, steps + 1).long()
 
-    def _solve(self, z_t, style_embedding, times, solver, eta):
+    def _solve(self, z_t, style_embedding, times, solver, eta, base_embedding=None, guidance_scale=1.0):
         if solver not in self._SOLVERS:
             raise ValueError(f"unknown solver {solver!r}: one of {sorted(self._SOLVERS)}")
-        return self._reverse(z_t, style_embedding, times, eta, order=self._SOLVERS[solver])
+        return self._reverse(z_t, style_embedding, times, eta, self._SOLVERS[solver], base_embedding, guidance_scale)
 
-    def style_conditioned_sample(self, z_t, style_embedding, steps=20, solver="dpmpp2m", t_start=None, eta=0.0):
+    def style_conditioned_sample(self, z_t, style_embedding, steps=20, solver="dpmpp2m", t_start=None, eta=0.0,
+                                 guidance_scale=1.0, base_embedding=None):
         """z_t at index t_start (default num_timesteps - 1) denoised in `steps` UNet passes over
         sample_times(t_start, steps).  solver: "dpmpp2m" (DPM-Solver++(2M), first-order first and last step),
         "dpmpp1" (its first-order form) or "ddim" (the reference's update, with eta, on this time grid).
-        Returns (x, logs) like style_conditioned_ddim_sample."""
+        Returns (x, logs) like style_conditioned_ddim_sample.
+
+        base_embedding (a style embedding with the target's key counts) and guidance_scale (a finite float or [B]):
+        every step steers the noise prediction from the base style towards the target, e_b + s (e_t - e_b): s = 1
+        samples the target, s > 1 exaggerates it, 0 < s < 1 applies it partly.  A scale other than 1 without a
+        base raises ValueError; scale 1 without a base is the unguided sampler."""
         t_start = self.num_timesteps - 1 if t_start is None else t_start
-        return self._solve(z_t, style_embedding, self.sample_times(t_start, steps), solver, eta)
+        return self._solve(z_t, style_embedding, self.sample_times(t_start, steps), solver, eta, base_embedding,
+                           guidance_scale)
 
     def content_style_transfer(self, content_spec, style_spec, t_start=99, steps=10, solver="dpmpp2m", noise=None,
-                               eta=0.0, style_weights=None):
+                               eta=0.0, style_weights=None, guidance_scale=1.0, base_style=None):
         """Encode content, q_sample it at index t_start (the strength), denoise over sample_times(t_start, steps)
         with `solver`, decode.  Returns (decoded, z_t_decoded) like content_style_transfer_wrapper.
 
@@ -601,7 +650,12 @@ class LDM(nn.Module):
         arguments and `steps` counts UNet passes, so the grids differ by design.
 
         style_spec [B,R,1,n_mels,F] with style_weights ([R] or [B,R], default equal) attends over R weighted
-        style references (encode_styles)."""
+        style references (encode_styles).
+
+        guidance_scale / base_style: style guidance (style_conditioned_sample).  base_style is a spectrogram
+        [B,1,n_mels,F] passed through the style encoder; None with a scale other than 1 takes the content
+        spectrogram itself ("away from how it sounds now, towards the target").  Against a mix of R references the
+        base is tiled R times (tile_embedding)."""
         if style_weights is not None and style_spec.dim() != 5:
             raise ValueError("style_weights needs a 5-D style_spec [B,R,1,n_mels,F]")
         content_spec = content_spec.float()
@@ -611,7 +665,16 @@ class LDM(nn.Module):
         t = torch.full((content_spec.shape[0],), int(t_start), dtype=torch.long)
         z_t, noise = self.noise_scheduler(z_0, t.to(content_spec.device), noise=noise)
         style_embedding = self._style_embedding(style_spec, style_weights)
-        sampled, _ = self._solve(z_t, style_embedding, times, solver, eta)
+        if UNetEngine.is_unguided(base_style, guidance_scale):
+            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta)
+        else:
+            UNetEngine.guidance_scale(guidance_scale, content_spec.shape[0])   # (validated before anything runs)
+            base_spec = content_spec if base_style is None else base_style.float()
+            base_embedding = self.style_encoder(base_spec)
+            R = int(style_embedding.get("refs", 1)) if isinstance(style_embedding, dict) else 1
+            if R > 1:
+                base_embedding = self.tile_embedding(base_embedding, R)
+            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale)
         decoded = self.decoder(sampled, rescale=True)
         z_t_decoded = self.decoder(z_t)
         return decoded, z_t_decoded

@@ -4,6 +4,7 @@ are crossfaded into one mel spectrogram that is vocoded once, so the phase is co
 
     python -m models.transfer --content a.wav --style b.wav --out c.wav [--checkpoint ldm.pth]
     python -m models.transfer --content a.wav --style b.wav c.wav --style-weights 0.7 0.3 --style-refs 2 --out o.wav
+    python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --guidance-scale 2.5 --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
 """
@@ -32,7 +33,7 @@ def style_window_indices(Ns, refs):
 
 def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, num_timesteps=100, eta=0.0,
                        batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None,
-                       style_weights=None, style_refs=1):
+                       style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -52,8 +53,27 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     and every content window attends over all of them at once (LDM.encode_styles) instead of being paired with one.
     style_weights: one weight per recording, or [N, recordings] per content window (a morph along the recording);
     default equal.  A recording's weight is shared equally among its windows.  At most LDM.MAX_STYLE_REFS windows
-    in all.  One recording, style_refs = 1 and no weights is the cyclic pairing above, unchanged."""
+    in all.  One recording, style_refs = 1 and no weights is the cyclic pairing above, unchanged.
+
+    Style guidance (needs a solver): guidance_scale s (a finite float) steers every step from a base style towards
+    the target, e_b + s (e_t - e_b) (LDM.content_style_transfer): s > 1 exaggerates the style, 0 < s < 1 applies
+    it partly.  base_style "content" (the default when s is not 1) takes each window's own content mel as the
+    base; a waveform [L] is windowed and paired like `style`.  s = 1 without a base_style is the unguided call."""
     n_mels = 128
+    guided = base_style is not None or float(guidance_scale) != 1.0
+    if guided:
+        if not math.isfinite(float(guidance_scale)):
+            raise ValueError(f"transfer_recording: guidance_scale must be finite, got {guidance_scale}")
+        if solver is None:
+            raise ValueError("transfer_recording: guidance_scale / base_style need a solver (the reference's sampler "
+                             "has no guidance)")
+        if base_style is None:
+            base_style = "content"
+        if not isinstance(base_style, str) and (base_style.dim() != 1 or base_style.numel() < audio.N_FFT // 2 + 1):
+            raise ValueError(f"transfer_recording: base_style must be \"content\" or a mono waveform [L] of at least "
+                             f"{audio.N_FFT // 2 + 1} samples")
+        if isinstance(base_style, str) and base_style != "content":
+            raise ValueError(f"transfer_recording: base_style must be \"content\" or a waveform, got {base_style!r}")
     styles = list(style) if isinstance(style, (list, tuple)) else [style]
     if not styles:
         raise ValueError("transfer_recording: no style recording")
@@ -91,6 +111,20 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     latent = model.unet.enc1.weight.shape[1]
     noise = torch.randn((N, latent, n_mels // 8, frames // 8), generator=torch.Generator().manual_seed(int(seed)))
     noise = noise.to(content.device)
+
+    def guide_kw(b0, b1):
+        """content_style_transfer's guidance arguments for windows [b0, b1): none when unguided."""
+        if not guided:
+            return {}
+        if isinstance(base_style, str):
+            return {"guidance_scale": float(guidance_scale), "base_style": x[b0:b1]}
+        return {"guidance_scale": float(guidance_scale), "base_style": xb[torch.arange(b0, b1, device=xb.device) % Nb]}
+
+    if guided and not isinstance(base_style, str):
+        Pb = audio.melspectrogram(base_style, sr=sr, n_mels=n_mels)
+        xb, _ = longform.mel_windows(Pb, frames, 0, max_db)
+        Nb = max(1, Pb.shape[-1] // frames)
+        xb = xb[:Nb]
     if mixing:
         refs = [xs[style_window_indices(Ns, style_refs)]]
         for y in styles[1:]:
@@ -118,7 +152,7 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                 else:
                     decoded, _ = model.content_style_transfer(x[b0:b1], spec, t_start=t_start, steps=num_timesteps,
                                                               solver=solver, eta=eta, noise=noise[b0:b1],
-                                                              style_weights=wb)
+                                                              style_weights=wb, **guide_kw(b0, b1))
                 out.append(decoded)
         return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N)
     pair = torch.arange(N, device=content.device) % Ns
@@ -133,7 +167,7 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
             else:
                 decoded, _ = model.content_style_transfer(x[b0:b1], xs[pair[b0:b1]], t_start=t_start,
                                                           steps=num_timesteps, solver=solver, eta=eta,
-                                                          noise=noise[b0:b1])
+                                                          noise=noise[b0:b1], **guide_kw(b0, b1))
             out.append(decoded)
     return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N)
 
@@ -180,6 +214,13 @@ def parse_args(argv=None):
                         "where --steps is also the noise level)")
     p.add_argument("--t-start", type=int, default=None, dest="t_start",
                    help="schedule index the content is noised at (needs --solver; default 99)")
+    p.add_argument("--guidance-scale", type=float, default=1.0, dest="guidance_scale",
+                   help="style strength s (needs --solver): every step steers the noise prediction from the base style "
+                        "towards the target, e_b + s (e_t - e_b); 1 = off, above 1 exaggerates the style, between 0 "
+                        "and 1 applies it partly")
+    p.add_argument("--base-style", default=None, dest="base_style", metavar="{content|PATH}",
+                   help="what the guidance steers away from: \"content\" (each window's own content, the default "
+                        "when --guidance-scale is not 1) or a .wav")
     p.add_argument("--batch", type=int, default=8, help="windows per model call")
     p.add_argument("--seed", type=int, default=0)
     args = p.parse_args(argv)
@@ -187,6 +228,10 @@ def parse_args(argv=None):
         p.error(f"--style-weights: {len(args.style_weights)} weights for {len(args.style)} --style files")
     if args.style_refs < 1:
         p.error("--style-refs must be positive")
+    if not math.isfinite(args.guidance_scale):
+        p.error("--guidance-scale must be finite")
+    if (args.guidance_scale != 1.0 or args.base_style is not None) and args.solver is None:
+        p.error("--guidance-scale / --base-style need --solver")
     if len(args.style) == 1:
         args.style = args.style[0]      # a single file: the string it always was
     return args
@@ -202,10 +247,16 @@ def main(argv=None):
     content = ap.trim_silence(content)
     style = styles[0] if len(styles) == 1 else styles
     model = load_model(args.checkpoint)
+    guide = {}
+    if args.guidance_scale != 1.0 or args.base_style is not None:   # (without the flags: today's call)
+        base = args.base_style
+        if base is not None and base != "content":
+            base = ap.trim_silence(ap.load_audio_native(base)[0])
+        guide = {"guidance_scale": args.guidance_scale, "base_style": base}
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
                              num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
                              solver=args.solver, t_start=args.t_start, style_weights=args.style_weights,
-                             style_refs=args.style_refs)
+                             style_refs=args.style_refs, **guide)
     ap.save_wav(args.out, res.audio, sr)
     print(f"{args.out}: {res.audio.numel() / sr:.1f} s, {res.N} windows of {args.frames} frames "
           f"({math.ceil(res.N / args.batch)} model calls)")
