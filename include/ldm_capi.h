@@ -449,6 +449,37 @@ int ldm_msolver_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w
 int ldm_guide_eps(const float* e_t, const float* e_b, const float* scale, int64_t per_sample, int32_t B, float* out,
                   void* stream);
 
+/* ---- regional transfer: hold masked content fixed (unet.hip sample_loop's Keep) ----------
+ * After every step's update the sampler state is blended with the content's own noising trajectory under a keep
+ * weight, per element in fp32, one rounding per operation (keep_blend, csrc/common.h):
+ *     known = a_i * z0 + b_i * n0;   x_next = (1 - w) * x_update + w * known
+ * z0 / n0 [B,C,H,W]: the clean latent and the q_sample noise; keep [B,H,W] in [0,1] (1 = keep the content, shared by
+ * the channels); keep_coef [nsteps,2] (device; ForwardDiffusion.keep_coefs).  The x0 / eps logs and the 2M history
+ * stay the model's own prediction.  The entries take the guided entries' argument list: a NULL base and a NULL scale
+ * mean unguided, S5 = S6 = 0 the maps' own key counts, key_bias* are optional.  With keep == NULL (then z0, n0 and
+ * keep_coef NULL as well) they are the existing entries argument for argument.  One of the four keep operands NULL
+ * beside the others, or a workspace whose allocation ends before ldm_ddim_workspace_floats_keep(.., guided)
+ * (checked like the guided entries' workspace), is an error reported before anything is launched.
+ * ldm_keep_blend: the same arithmetic on whole NCHW tensors, in place on x, with one row coef = {a, b}. */
+int64_t ldm_ddim_workspace_floats_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5,
+                                       int32_t S6, int32_t guided);
+int ldm_ddim_sample_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
+                         const float* s5_base, const float* s6_base, int32_t S5, int32_t S6, const float* key_bias5,
+                         const float* key_bias6, const float* key_bias5_base, const float* key_bias6_base,
+                         const float* guide_scale, const float* z0, const float* n0, const float* keep,
+                         const float* keep_coef, const int64_t* t_table, const float* coef_table, int32_t nsteps,
+                         float eta, float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
+                         void* stream);
+int ldm_msolver_sample_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                            const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
+                            const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
+                            const float* key_bias6_base, const float* guide_scale, const float* z0, const float* n0,
+                            const float* keep, const float* keep_coef, const int64_t* t_table, const float* coef_table,
+                            int32_t nsteps, float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
+                            void* stream);
+int ldm_keep_blend(float* x, const float* z0, const float* n0, const float* keep, const float* coef, int32_t B, int32_t C,
+                   int64_t HW, void* stream);
+
 /* ---- data formats either side of the path (dataio.hip) ---------------------------
  * ldm_mel_quantize: the reference's 8-bit mel PNG pixels, uint8(clip((db + max_db) * 255/max_db, 0, 255)
  * + 0.5) (audio_processor.py:55-73, fp32 arithmetic, bit-exact with its numpy); ldm_mel_dequantize: its

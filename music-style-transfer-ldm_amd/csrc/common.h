@@ -199,6 +199,14 @@ struct EpiArgs {
     const float* guide_eb;
     const float* guide_scale;
     float* ddim_x2;
+    // regional keep behind either fused update (keep_blend): the new state is blended with the content's own noising
+    // trajectory keep_coef[0] * keep_z0 + keep_coef[1] * keep_n0 (both laid out like ddim_x) under the keep weight
+    // keep_w ([B, Hout, Wout], shared by the channels) before it is stored; the logs stay the model's own prediction.
+    // NULL keep_w: no keep.
+    const float* keep_z0;
+    const float* keep_n0;
+    const float* keep_w;
+    const float* keep_coef;
 };
 
 // conv.hip: implicit-GEMM conv with the full internal epilogue (incl. the fused DDIM update); y may be
@@ -257,6 +265,13 @@ struct StepConv {
     const float* guide_eb;
     const float* guide_scale;
     float* xs2;
+    // dec1 with the regional keep (EPI_KEEP, uconv_keep.hip): keep_base = the loop's keep region, [z0 | n0 | w] with
+    // z0 / n0 NHWC like xs and w [B, H, W], in the guided loop [e_b | z0 | n0 | w] (guide_eb == keep_base);
+    // keep_row = this step's row {a, b}, in the guided loop {a, b, scale[B]} (guide_scale is then unused)
+    // keep_stride = the floats between the region's parts (one state: B C H W of the loop that laid it out)
+    const float* keep_base;
+    const float* keep_row;
+    int64_t keep_stride;
     float* ws;            // split-K workspace (step_ws_floats; zero-filled once) for the K-split layers
 };
 int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st);
@@ -317,6 +332,23 @@ __device__ __forceinline__ float guide_eps(float e_t, float e_b, float s) {
     const float d = e_t - e_b;
     const float g = s * d;
     return e_b + g;
+}
+
+// Regional keep for one element, after the step's update: xu (what ddim_update / msolver_update returned) blended with
+// the content's own noising trajectory known = a z0 + b n0 under the keep weight w in [0, 1], with the same rounding
+// discipline.  w = 0 gives xu and w = 1 gives known, both exactly (finite inputs: 1 * v and v + 0 are exact, and
+// 0 * v is a zero of either sign, which changes no sum except that -0 + 0 = +0).  With z0 / n0 the operands of the
+// q_sample that produced x and (a, b) = (sqrt(ab_next), sqrt(1 - ab_next)), known is where a perfect denoiser's
+// DDIM (eta 0) trajectory stands after the step.
+__device__ __forceinline__ float keep_blend(float xu, float z0, float n0, float w, float a, float b) {
+#pragma clang fp contract(off)
+    const float k = a * z0;
+    const float n = b * n0;
+    const float known = k + n;
+    const float u = 1.0f - w;
+    const float p = u * xu;
+    const float q = w * known;
+    return p + q;
 }
 
 // v rounded to a 16-bit type (LDM_DT_F16 / LDM_DT_BF16, round to nearest even), or unchanged (0)

@@ -1646,6 +1646,8 @@ int conv_forward_ex(const ldm_conv_desc& d, const ldm_conv_plan& p, const float*
                 "conv forward: fused multistep update needs x and its x0 log, and excludes the DDIM one");
     LDM_REQUIRE(!ep.guide_eb || ((ep.ddim_coef || ep.ms_coef) && ep.guide_scale && ep.ddim_x2),
                 "conv forward: style guidance goes in front of a fused update and needs its scales and second state");
+    LDM_REQUIRE(!ep.keep_w || ((ep.ddim_coef || ep.ms_coef) && ep.keep_z0 && ep.keep_n0 && ep.keep_coef && !((d.layout >> 1) & 1)),
+                "conv forward: the regional keep goes behind a fused update (NCHW) and needs z0, n0 and its coefficients");
     if (p.kind == 3) return tconv_forward(d, p, x, w, ep, y, st);
     if (p.kind == 4) return sconv_forward(d, p, x, w, ep, y, st);
     ConvArgs a;

@@ -1,6 +1,7 @@
 // ConvArgs and the conv epilogue (conv.hip's implicit-GEMM kernels and sconv.hip's small-plane kernel share them):
 // the reference's op order conv + bias -> BN(eval) -> act -> + bcast -> + skip (model.py:16-25, :205-229), with
-// autocast output rounding and the fused DDIM / multistep-solver update, optionally behind style guidance.
+// autocast output rounding and the fused DDIM / multistep-solver update, optionally behind style guidance
+// and in front of the regional keep.
 #pragma once
 #include "common.h"
 
@@ -125,10 +126,18 @@ __device__ __forceinline__ void epi_finish(const ConvArgs& a, int m, size_t oidx
         v = guide_eps(v, e.guide_eb[oidx], e.guide_scale[oidx / per]);
         x2 = e.ddim_x2;
     }
+    // regional keep (uniform): the update's result blended with the content's trajectory before it is stored
+    auto keep = [&](float xu) {
+        if (!e.keep_w) return xu;
+        const size_t hw = (size_t)a.Hout * a.Wout;
+        const size_t bi = oidx / (hw * a.Cout);
+        return keep_blend(xu, e.keep_z0[oidx], e.keep_n0[oidx], e.keep_w[bi * hw + oidx % hw], e.keep_coef[0],
+                          e.keep_coef[1]);
+    };
     if (e.ms_coef) {   // the multistep solver's update (uniform branches; its history is read here, not prefetched)
         const bool hp = e.ms_x0_prev != nullptr;
         float x0;
-        const float xn = msolver_update(p.x, v, e.ms_coef, hp, hp ? e.ms_x0_prev[oidx] : 0.f, x0);
+        const float xn = keep(msolver_update(p.x, v, e.ms_coef, hp, hp ? e.ms_x0_prev[oidx] : 0.f, x0));
         e.ddim_x[oidx] = xn;
         if (x2) x2[oidx] = xn;
         e.ddim_x0_log[oidx] = x0;
@@ -138,7 +147,7 @@ __device__ __forceinline__ void epi_finish(const ConvArgs& a, int m, size_t oidx
     }
     if (e.ddim_coef) {
         float x0;
-        const float xn = ddim_update(p.x, v, e.ddim_coef, e.ddim_eta, x0);
+        const float xn = keep(ddim_update(p.x, v, e.ddim_coef, e.ddim_eta, x0));
         e.ddim_x[oidx] = xn;
         if (x2) x2[oidx] = xn;
         if (e.ddim_x0_log) e.ddim_x0_log[oidx] = x0;

@@ -631,6 +631,17 @@ __global__ __launch_bounds__(256) void guide_eps_kernel(const float* e_t, const 
     out[i] = guide_eps(e_t[i], e_b[i], scale[i / per_sample]);
 }
 
+// The regional keep on whole NCHW tensors, in place on x (the per-layer sampling path, after the update kernels):
+// x = keep_blend(x, z0, n0, keep[sample, pixel], coef[0], coef[1]); keep is [B, HW], shared by the C channels.
+__global__ __launch_bounds__(256) void keep_blend_kernel(float* __restrict__ x, const float* __restrict__ z0,
+                                                         const float* __restrict__ n0, const float* __restrict__ keep,
+                                                         const float* __restrict__ coef, int64_t C, int64_t HW, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t b = i / (C * HW);
+    x[i] = keep_blend(x[i], z0[i], n0[i], keep[b * HW + i % HW], coef[0], coef[1]);
+}
+
 // (train-mode BatchNorm2d lives in reduce.hip)
 
 __global__ __launch_bounds__(256) void activation_kernel(const float* x, float* y, int64_t n, int act) {
@@ -925,6 +936,16 @@ extern "C" int ldm_guide_eps(const float* e_t, const float* e_b, const float* sc
     hipLaunchKernelGGL(guide_eps_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, e_t, e_b, scale,
                        per_sample, n, out);
     LDM_CHECK_LAUNCH("guide_eps_kernel");
+    return 0;
+}
+
+extern "C" int ldm_keep_blend(float* x, const float* z0, const float* n0, const float* keep, const float* coef, int32_t B,
+                              int32_t C, int64_t HW, void* stream) {
+    LDM_REQUIRE(x && z0 && n0 && keep && coef && B > 0 && C > 0 && HW > 0, "keep_blend: bad argument");
+    const int64_t n = (int64_t)B * C * HW;
+    hipLaunchKernelGGL(keep_blend_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, z0, n0, keep,
+                       coef, (int64_t)C, HW, n);
+    LDM_CHECK_LAUNCH("keep_blend_kernel");
     return 0;
 }
 

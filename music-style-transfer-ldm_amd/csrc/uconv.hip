@@ -38,16 +38,24 @@
         if (_rc) return _rc;     \
     } while (0)
 
+#if defined(UCONV_GUIDE_TU) || defined(UCONV_KEEP_TU)
+#define UCONV_TEMPLATES_ONLY 1   // (a translation unit of dec1 instances only: uconv_guide.hip, uconv_keep.hip)
+#endif
+
 namespace ldm {
 namespace uc {
 
-enum : int { EPI_RELU = 1, EPI_BCAST = 2, EPI_SKIP = 4, EPI_POSB = 8, EPI_DDIM = 16, EPI_PLANE = 32, EPI_WINDOW = 64, EPI_MSOLVER = 128, EPI_GUIDE = 256 };
+enum : int { EPI_RELU = 1, EPI_BCAST = 2, EPI_SKIP = 4, EPI_POSB = 8, EPI_DDIM = 16, EPI_PLANE = 32, EPI_WINDOW = 64, EPI_MSOLVER = 128, EPI_GUIDE = 256, EPI_KEEP = 512 };
 // EPI_MSOLVER: dec1's epilogue is the multistep solver's update (msolver_update) in place of EPI_DDIM's; its
 // instances are separate ones, so the EPI_DDIM instances are compiled exactly as without it.
 // EPI_GUIDE (with EPI_DDIM or EPI_MSOLVER, again as separate instances): dec1 of the guided loop's target half.  The
 // launch covers the caller's B samples; the base half's noise prediction e_b (written just before by the same
 // geometry as a plain conv, NHWC) and the sample's strength are prefetched with the other epilogue operands, the
 // output becomes guide_eps(o, e_b, s) before the update, and the new state is stored to both halves' copies.
+// EPI_KEEP (with EPI_DDIM or EPI_MSOLVER, with or without EPI_GUIDE, separate instances once more): the regional keep.
+// The update's result is blended with the content's own noising trajectory (keep_blend) before it is stored; z0, n0,
+// the pixel's keep weight and the step's (a, b) are prefetched with the other epilogue operands.  The logs stay the
+// model's own prediction.
 // EPI_PLANE (a geometry flag carried with the epilogue bits): the layer's plane is 2 x 8 (the bottleneck at the
 // canonical 16 x 64 latent), so the 16 columns of a lane group are one sample's whole plane and every tap of a
 // stride-1 3x3 conv reads a position some lane of the group already holds.  Each channel chunk's activation
@@ -85,6 +93,9 @@ struct UArgs {
     // EPI_GUIDE adds no field (the kernarg block of every step launch stays the size it was): it reads the base half's
     // noise prediction (NHWC like xs) from `skip`, the guidance strength per sample [B] from `bcast`, and stores the
     // base half's copy of the sampler state through `y`: the three slots dec1's fused update leaves unused
+    // EPI_KEEP adds none either.  `skip` is the loop's keep region [z0 | n0 | w] (z0 / n0 NHWC like xs, w [B, H, W])
+    // and `bcast` the step's row {a, b}; with EPI_GUIDE the region is [e_b | z0 | n0 | w] and the row
+    // {a, b, scale[B]}, so e_b is still read from `skip` and the strengths from `bcast`, two floats further on
 };
 
 // (ky, kx) of tap t and the conv input offset / the transposed conv's output parity
@@ -359,8 +370,9 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
         o.ok = f < NFR && colsel(cval, ni) != 0;
         return o;
     };
-    floatx4 pre_b[NMY], pre_c[NMY], pre_s[NMY], pre_h[NMY], pre_g[NMY];
-    float pre_gs[NMY];
+    floatx4 pre_b[NMY], pre_c[NMY], pre_s[NMY], pre_h[NMY], pre_g[NMY], pre_kz[NMY], pre_kn[NMY];
+    float pre_gs[NMY], pre_kw[NMY], pre_ka = 0.f, pre_kb = 0.f;
+    constexpr int KROW = (EPI & EPI_KEEP) ? 2 : 0;   // the strengths' offset in `bcast`
     auto epi_prefetch = [&]() {
         static_for<0, NMY>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
@@ -382,9 +394,17 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
             }
             if constexpr ((EPI & EPI_GUIDE) != 0) {
                 pre_g[k] = *reinterpret_cast<const floatx4*>(a.skip + (size_t)o.pix * COUT + o.m);
-                pre_gs[k] = a.bcast[o.b];
+                pre_gs[k] = a.bcast[KROW + o.b];
+            }
+            if constexpr ((EPI & EPI_KEEP) != 0) {
+                constexpr int G = (EPI & EPI_GUIDE) ? 1 : 0;   // e_b in front of the keep operands
+                const size_t ne = (size_t)a.B * a.Hout * a.Wout * COUT;
+                pre_kz[k] = *reinterpret_cast<const floatx4*>(a.skip + G * ne + (size_t)o.pix * COUT + o.m);
+                pre_kn[k] = *reinterpret_cast<const floatx4*>(a.skip + (G + 1) * ne + (size_t)o.pix * COUT + o.m);
+                pre_kw[k] = a.skip[(G + 2) * ne + (size_t)o.pix];
             }
         });
+        if constexpr ((EPI & EPI_KEEP) != 0) pre_ka = a.bcast[0], pre_kb = a.bcast[1];
     };
 
     // scheduling fences keep each stage's loads ahead of the MFMAs that consume the previous stage (the
@@ -732,6 +752,10 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
                 a.x0_log[lbase + r * hw] = x0;
                 if (a.eps_log) a.eps_log[lbase + r * hw] = o[r];
             }
+            if constexpr ((EPI & EPI_KEEP) != 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) xn[r] = keep_blend(xn[r], pre_kz[k][r], pre_kn[k][r], pre_kw[k], pre_ka, pre_kb);
+            }
             *reinterpret_cast<floatx4*>(a.xs + (size_t)ot.pix * COUT + ot.m) = xn;
             if constexpr ((EPI & EPI_GUIDE) != 0) *reinterpret_cast<floatx4*>(a.y + (size_t)ot.pix * COUT + ot.m) = xn;
         } else if constexpr ((EPI & EPI_DDIM) != 0) {
@@ -746,6 +770,10 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
                 xn[r] = ddim_update(xv[r], o[r], a.coef, a.eta, x0);
                 if (a.x0_log) a.x0_log[lbase + r * hw] = x0;
                 if (a.eps_log) a.eps_log[lbase + r * hw] = o[r];
+            }
+            if constexpr ((EPI & EPI_KEEP) != 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) xn[r] = keep_blend(xn[r], pre_kz[k][r], pre_kn[k][r], pre_kw[k], pre_ka, pre_kb);
             }
             *reinterpret_cast<floatx4*>(a.xs + (size_t)ot.pix * COUT + ot.m) = xn;
             if constexpr ((EPI & EPI_GUIDE) != 0) *reinterpret_cast<floatx4*>(a.y + (size_t)ot.pix * COUT + ot.m) = xn;
@@ -797,7 +825,7 @@ __global__ __launch_bounds__(256) void uconv_pack_kernel(const float* __restrict
         reinterpret_cast<__bf16*>(outp)[idx] = (__bf16)v;
 }
 
-#ifndef UCONV_GUIDE_TU
+#ifndef UCONV_TEMPLATES_ONLY
 // NCHW <-> NHWC for the sampler state (once before / after the loop)
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, int C,
                                                            int HW, int64_t n) {
@@ -873,7 +901,34 @@ static int launch(const UArgs& a, int dtype, hipStream_t st) {
 // step kernels holds exactly the instances it held without guidance.  geo: 0 variant 3 windowed, 1 / 2 the thin form
 // with / without the window, 3 / 4 the 32-row form with / without it.
 int step_dec1_guided(int geo, const UArgs& a, const StepConv& s, hipStream_t st);
-#ifdef UCONV_GUIDE_TU
+// dec1 with the regional keep, guided or not, likewise (uconv_keep.hip, UCONV_KEEP_TU); the guided loop's plain base
+// half stays step_dec1_guided's
+int step_dec1_keep(int geo, const UArgs& a, const StepConv& s, hipStream_t st);
+#ifdef UCONV_KEEP_TU
+template <int TM, int TN, int WN, int WK, int NCH, int S, int GEO, int KS = 1>
+static int launch_dec1_keep(const UArgs& a, const StepConv& s, hipStream_t st) {
+    LDM_REQUIRE(s.xs && s.coef && !s.plain, "dec1 (keep): sampler state, coefficients");
+    if (s.guide_eb) {
+        if (s.msolver)
+            return launch<0, 64, 32, TM, TN, WN, WK, NCH, S, EPI_MSOLVER | EPI_GUIDE | EPI_KEEP | GEO, KS>(a, s.dtype, st);
+        return launch<0, 64, 32, TM, TN, WN, WK, NCH, S, EPI_DDIM | EPI_GUIDE | EPI_KEEP | GEO, KS>(a, s.dtype, st);
+    }
+    if (s.msolver) return launch<0, 64, 32, TM, TN, WN, WK, NCH, S, EPI_MSOLVER | EPI_KEEP | GEO, KS>(a, s.dtype, st);
+    return launch<0, 64, 32, TM, TN, WN, WK, NCH, S, EPI_DDIM | EPI_KEEP | GEO, KS>(a, s.dtype, st);
+}
+int step_dec1_keep(int geo, const UArgs& a, const StepConv& s, hipStream_t st) {
+    switch (geo) {
+        case 0: return launch_dec1_keep<1, 2, 2, 4, 9, 9, EPI_WINDOW, 1>(a, s, st);
+        case 1: return launch_dec1_keep<1, 2, 2, 2, 18, 18, EPI_WINDOW>(a, s, st);
+        case 2: return launch_dec1_keep<1, 2, 2, 2, 18, 18, 0>(a, s, st);
+        case 3: return launch_dec1_keep<2, 2, 1, 4, 9, 9, EPI_WINDOW>(a, s, st);
+        case 4: return launch_dec1_keep<2, 2, 1, 4, 9, 9, 0>(a, s, st);
+        default: return fail(2, "step conv: unknown keep dec1 geometry");
+    }
+}
+}  // namespace uc
+}  // namespace ldm
+#elif defined(UCONV_GUIDE_TU)
 // on geometry (TM, TN, WN, WK, NCH, S; GEO = EPI_WINDOW or 0): the base half as a plain conv, or the target half with
 // the guided DDIM / multistep update
 template <int TM, int TN, int WN, int WK, int NCH, int S, int GEO, int KS = 1>
@@ -1163,6 +1218,7 @@ static int make_args(int layer, int B, int H, int W, const StepConv& s, int ksv,
     a.eta = s.eta;
     a.x0_prev = s.x0_prev;
     if (s.guide_eb) a.skip = s.guide_eb, a.bcast = s.guide_scale, a.y = s.xs2;   // (EPI_GUIDE's slots, see UArgs)
+    if (s.keep_base) a.skip = s.keep_base, a.bcast = s.keep_row;                 // (EPI_KEEP's, likewise)
     a.B = B;
     a.Hin = Hin;
     a.Win = Win;
@@ -1215,7 +1271,13 @@ static int make_args(int layer, int B, int H, int W, const StepConv& s, int ksv,
     LDM_REQUIRE(!s.msolver || (layer == 8 && s.x0_log), "step conv: the multistep update is dec1's and needs its x0 log");
     LDM_REQUIRE((!s.plain && !s.guide_eb) || layer == 8, "step conv: the guided loop's two launches are dec1's");
     LDM_REQUIRE(!s.plain || (s.y && !s.guide_eb), "step conv: dec1's base half is a plain conv into y");
-    LDM_REQUIRE(!s.guide_eb || (s.guide_scale && s.xs2 && s.xs2 != s.xs), "step conv: guidance needs its scales and second state");
+    LDM_REQUIRE(!s.guide_eb || ((s.guide_scale || s.keep_base) && s.xs2 && s.xs2 != s.xs),
+                "step conv: guidance needs its scales and second state");
+    LDM_REQUIRE(!s.keep_base || (layer == 8 && !s.plain && s.keep_row && (!s.guide_eb || s.guide_eb == s.keep_base)),
+                "step conv: the regional keep is dec1's and needs its region and row (e_b leading the region when guided)");
+    // (the kernel finds z0 / n0 / w behind skip by its own launch shape: it must be the shape the region was laid out for)
+    LDM_REQUIRE(!s.keep_base || (int64_t)a.B * a.Hout * a.Wout * g.cout == s.keep_stride,
+                "step conv: the keep region was laid out for another batch or plane than this launch's");
     return 0;
 }
 }  // namespace uc
@@ -1240,6 +1302,7 @@ int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st)
             case 7: LDM_REQUIRE(s.y && s.skip && win && a.Wq % 32 == 0, "dec2 (variant 3): y, skip, 32-column rows");
                 return launch<2, 128, 64, 1, 2, 1, 8, 9, 9, EPI_RELU | EPI_SKIP | EPI_WINDOW, 1>(a, s.dtype, st);
             case 8: LDM_REQUIRE(win && a.Wq % 64 == 0, "dec1 (variant 3): 64-column rows");
+                if (s.keep_base) return step_dec1_keep(0, a, s, st);
                 if (guided) return step_dec1_guided(0, a, s, st);
                 LDM_REQUIRE(s.xs && s.coef, "dec1 (variant 3): sampler state");
                 if (s.msolver) return launch<0, 64, 32, 1, 2, 2, 4, 9, 9, EPI_MSOLVER | EPI_WINDOW, 1>(a, s.dtype, st);
@@ -1326,7 +1389,11 @@ int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st)
                 return launch<2, 128, 64, 1, 2, 1, 4, 18, 18, EPI_RELU | EPI_SKIP | EPI_WINDOW>(a, s.dtype, st);
             return launch<2, 128, 64, 1, 2, 1, 4, 18, 18, EPI_RELU | EPI_SKIP>(a, s.dtype, st);
         default:
-            if (guided) {   // the same four geometries
+            if (s.keep_base) {   // the same four geometries
+                if (dec1_thin(W)) return step_dec1_keep(window_taps() ? 1 : 2, a, s, st);
+                return step_dec1_keep(window_taps() && a.Wq % 32 == 0 ? 3 : 4, a, s, st);
+            }
+            if (guided) {
                 if (dec1_thin(W)) {
                     if (window_taps()) return step_dec1_guided(1, a, s, st);
                     return step_dec1_guided(2, a, s, st);
@@ -1483,4 +1550,4 @@ extern "C" int ldm_step_conv_dt(int32_t layer, int32_t B, int32_t H, int32_t W, 
     LDM_REQUIRE(layer != 8, "ldm_step_conv: dec1 runs fused with the DDIM update (ldm_ddim_sample)");
     return step_conv(layer, B, H, W, s, (hipStream_t)stream);
 }
-#endif   // UCONV_GUIDE_TU
+#endif   // UCONV_TEMPLATES_ONLY

@@ -196,7 +196,18 @@ struct DdimFuse {
     int gB;
     float* eb;
     const float* gscale;
+    // regional keep (keep_blend behind the update), kw == NULL: none.  conv.hip's loops read the caller's NCHW z0 / n0
+    // and [B, H, W] weights with the step's row kcoef = {a, b}; the step kernels read the loop's keep region kbase
+    // ([z0 | n0 | w], NHWC, led by e_b when guided: eb == kbase) and the step's row krow ({a, b}, then the strengths)
+    const float *kz0, *kn0, *kw, *kcoef;
+    const float *kbase, *krow;
+    int64_t kstride;   // floats between the region's parts
 };
+
+static void keep_epi(EpiArgs& ep, const DdimFuse* fuse) {
+    if (!fuse || !fuse->kw) return;
+    ep.keep_z0 = fuse->kz0, ep.keep_n0 = fuse->kn0, ep.keep_w = fuse->kw, ep.keep_coef = fuse->kcoef;
+}
 
 static int conv_call(const ldm_unet_shape& s, float* convws, int layer, const ldm_conv_plan& plan, const float* x, const float* w,
                      const float* bias, int act, const float* bcast, const float* skip, float* y, hipStream_t st,
@@ -217,6 +228,7 @@ static int conv_call(const ldm_unet_shape& s, float* convws, int layer, const ld
         ep.ddim_x = fuse->x;
         ep.ddim_x0_log = fuse->x0_log;
         ep.ddim_eps_log = fuse->eps_log;
+        keep_epi(ep, fuse);
     }
     return conv_forward_ex(d, plan, x, w, ep, y, convws, st);
 }
@@ -259,6 +271,7 @@ static int dec1_call(const ldm_unet_shape& s, const ldm_unet_weights& w, const f
     ep.guide_eb = fuse->eb;
     ep.guide_scale = fuse->gscale;
     ep.ddim_x2 = fuse->x + fuse->gB * HW * s.C;
+    keep_epi(ep, fuse);
     return conv_forward_ex(d, plan, d2, w.conv_w[8], ep, nullptr, convws, st);
 }
 
@@ -385,6 +398,7 @@ static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w,
     c[8].eps_log = fuse.eps_log;
     c[8].msolver = fuse.msolver;
     c[8].x0_prev = fuse.x0_prev;
+    if (fuse.kw && !fuse.gB) c[8].keep_base = fuse.kbase, c[8].keep_row = fuse.krow, c[8].keep_stride = fuse.kstride;
     auto dec1_guided = [&]() -> int {   // the base half into eb, then the target half guided against it
         const int Bh = fuse.gB;
         StepConv cb = c[8];
@@ -397,6 +411,8 @@ static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w,
         ct.guide_eb = fuse.eb;
         ct.guide_scale = fuse.gscale;
         ct.xs2 = ws.xs + (size_t)Bh * HW * s.C;
+        if (fuse.kw)   // (eb == kbase)
+            ct.keep_base = fuse.kbase, ct.keep_row = fuse.krow, ct.keep_stride = fuse.kstride, ct.guide_scale = nullptr;
         return step_conv(8, Bh, s.H, s.W, ct, st);
     };
     auto run = [&](int l0, int l1) -> int {   // layers [l0, l1]
@@ -475,6 +491,28 @@ extern "C" int ldm_unet_forward(const ldm_unet_shape* s, const ldm_unet_weights*
 struct Guide {
     const float *s5_base, *s6_base, *key_bias5_base, *key_bias6_base, *scale;
 };
+// The regional keep (the *_keep entries, k != NULL): after every step's update the state is blended with the content's
+// own noising trajectory coef[i][0] z0 + coef[i][1] n0 under the keep weights w [B, H, W] (keep_blend); the logs and
+// the 2M history stay the model's prediction.  Only dec1's epilogue differs.  The step kernels read z0 / n0 in the
+// state's NHWC layout from a keep region behind the time embeddings (keep_region_floats), filled once per loop.
+struct Keep {
+    const float *z0, *n0, *w, *coef;
+};
+// [e_b (guided)] [z0] [n0] [w] [nsteps rows {a, b, scale[B] (guided)}]
+static int64_t keep_region_floats(const ldm_unet_shape& s, int32_t nsteps, bool guided) {
+    const int64_t HW = (int64_t)s.H * s.W, dense = s.B * s.C * HW;
+    return (guided ? 3 : 2) * dense + s.B * HW + (int64_t)nsteps * (2 + (guided ? s.B : 0));
+}
+// rows[i] = {coef[i][0], coef[i][1], scale[0 .. B)} (scale NULL: rows of two)
+__global__ __launch_bounds__(256) void keep_rows_kernel(const float* __restrict__ coef, const float* __restrict__ scale,
+                                                        float* __restrict__ rows, int B, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // over rows
+    if (i >= n) return;
+    const int rl = 2 + (scale ? B : 0);
+    const int64_t r = i / rl;
+    const int j = (int)(i - r * rl);
+    rows[i] = j < 2 ? coef[2 * r + j] : scale[j - 2];
+}
 
 // out[r] = a[r] ++ b[r] for rows of rowlen floats (NULL a / b: zeros): the doubled batch's operands, once per loop
 __global__ __launch_bounds__(256) void concat_halves_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -496,7 +534,7 @@ static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, floa
                        const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta, float* x0_logs,
                        float* eps_logs, int64_t log_step_stride, float* workspace, void* stream, bool msolver,
                        int32_t S5 = 0, int32_t S6 = 0, const float* key_bias5 = nullptr,
-                       const float* key_bias6 = nullptr, const Guide* g = nullptr) {
+                       const float* key_bias6 = nullptr, const Guide* g = nullptr, const Keep* kp = nullptr) {
     ldm_unet_shape sh = *sc;   // the shape the body runs at
     if (g) sh.B = 2 * sc->B;
     const ldm_unet_shape* s = &sh;
@@ -550,6 +588,7 @@ static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, floa
                       eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
                       msolver && i > 0 ? x0_logs + (size_t)(i - 1) * n : nullptr};
         if (g) fuse.gB = sc->B, fuse.eb = ws.eb, fuse.gscale = g->scale;
+        if (kp) fuse.kz0 = kp->z0, fuse.kn0 = kp->n0, fuse.kw = kp->w, fuse.kcoef = kp->coef + 2 * (size_t)i;
         return fuse;
     };
     if (w->use_fold) {
@@ -569,8 +608,25 @@ static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, floa
             if (bfold) LDM_TRY(bneck_fold_values(w->step_bneck_w, ws.kv1, ws.ubn, s->B, st));
             LDM_TRY(step_layout(x, ws.xs, sc->B, s->C, HW, true, st));
             if (g) LDM_TRY(step_layout(x, ws.xs + dense, sc->B, s->C, HW, true, st));
+            float* kreg = temb_all + (size_t)nsteps * (g ? 3 : 1) * sc->B * 128;   // the keep region
+            const int krl = 2 + (g ? sc->B : 0);
+            float* krows = kreg + (g ? 3 : 2) * dense + (int64_t)sc->B * HW;
+            if (kp) {
+                float* kz = kreg + (g ? dense : 0);
+                LDM_TRY(step_layout(kp->z0, kz, sc->B, s->C, HW, true, st));
+                LDM_TRY(step_layout(kp->n0, kz + dense, sc->B, s->C, HW, true, st));
+                LDM_HIP_TRY(hipMemcpyAsync(kz + 2 * dense, kp->w, (size_t)sc->B * HW * 4, hipMemcpyDeviceToDevice, st));
+                const int64_t nr = (int64_t)nsteps * krl;
+                hipLaunchKernelGGL(keep_rows_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, kp->coef,
+                                   g ? g->scale : nullptr, krows, sc->B, nr);
+                LDM_CHECK_LAUNCH("keep_rows_kernel");
+            }
             for (int i = 0; i < nsteps; ++i) {
-                const DdimFuse fuse = make_fuse(i, ws.xs);
+                DdimFuse fuse = make_fuse(i, ws.xs);
+                if (kp) {
+                    fuse.kbase = kreg, fuse.krow = krows + (size_t)i * krl, fuse.kstride = dense;
+                    if (g) fuse.eb = kreg;   // e_b leads the keep region
+                }
                 LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold));
             }
             return step_layout(ws.xs, x, sc->B, s->C, HW, false, st);
@@ -673,8 +729,8 @@ extern "C" int64_t ldm_ddim_workspace_floats_guided(const ldm_unet_shape* s, con
 // allocation that holds `workspace` is asked of the runtime and compared with the guided size.  This is exact for a
 // buffer that is an allocation of its own; a buffer carved from a larger pool is only known to end inside the pool.
 // Skipped under stream capture (a captured loop is run eagerly first) and where the runtime does not know the pointer.
-static int guided_workspace_ok(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5, int32_t S6,
-                               const float* workspace, void* stream) {
+// need: the size in floats the entry's own function gives (ldm_ddim_workspace_floats_guided / _keep), named by `fn`.
+static int workspace_extent_ok(int64_t need, const char* fn, const float* workspace, void* stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
         (void)hipGetLastError();
@@ -687,12 +743,16 @@ static int guided_workspace_ok(const ldm_unet_shape* s, const ldm_unet_weights* 
         (void)hipGetLastError();
         return 0;
     }
-    const int64_t need = ldm_ddim_workspace_floats_guided(s, w, nsteps, S5, S6);
-    LDM_REQUIRE(need > 0, "guided sample: bad shape for the workspace size");
+    LDM_REQUIRE(need > 0, "guided / keep sample: bad shape for the workspace size");
     const int64_t avail = (int64_t)(((const char*)base + size) - (const char*)workspace);
-    LDM_REQUIRE(avail >= need * 4, "guided sample: the workspace's allocation ends before the size "
-                                   "ldm_ddim_workspace_floats_guided gives (was it sized by ldm_ddim_workspace_floats?)");
+    LDM_REQUIRE(avail >= need * 4, std::string("guided / keep sample: the workspace's allocation ends before the size ") + fn +
+                                       " gives (was it sized by another workspace function?)");
     return 0;
+}
+static int guided_workspace_ok(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5, int32_t S6,
+                               const float* workspace, void* stream) {
+    return workspace_extent_ok(ldm_ddim_workspace_floats_guided(s, w, nsteps, S5, S6), "ldm_ddim_workspace_floats_guided",
+                               workspace, stream);
 }
 
 static int guided_args_ok(const ldm_unet_shape* s, const float* s5_base, const float* s6_base, const float* guide_scale,
@@ -744,4 +804,70 @@ extern "C" int ldm_msolver_sample_guided(const ldm_unet_shape* s, const ldm_unet
     const Guide g{s5_base, s6_base, key_bias5_base, key_bias6_base, guide_scale};
     return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs, log_step_stride, workspace,
                        stream, true, S5, S6, key_bias5, key_bias6, &g);
+}
+
+// ---- regional keep: the same loops with the state held on the content's trajectory under a mask (sample_loop's Keep)
+extern "C" int64_t ldm_ddim_workspace_floats_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps,
+                                                  int32_t S5, int32_t S6, int32_t guided) {
+    if (!s || nsteps < 0 || S5 < 0 || S6 < 0 || s->B <= 0) return -1;
+    int64_t base;
+    if (guided) {
+        base = ldm_ddim_workspace_floats_guided(s, w, nsteps, S5, S6);
+    } else {
+        const int L2 = s->H * s->W / 16, L1 = s->H * s->W / 64;
+        base = carve(*s, w, nullptr, S5 > 0 ? S5 : L2, S6 > 0 ? S6 : L1).total + (int64_t)nsteps * s->B * 128;
+    }
+    return base < 0 ? base : base + keep_region_floats(*s, nsteps, guided != 0);
+}
+
+static int keep_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
+                       const float* s5_base, const float* s6_base, int32_t S5, int32_t S6, const float* key_bias5,
+                       const float* key_bias6, const float* key_bias5_base, const float* key_bias6_base,
+                       const float* guide_scale, const float* z0, const float* n0, const float* keep,
+                       const float* keep_coef, const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta,
+                       float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace, void* stream,
+                       bool msolver) {
+    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace && (!msolver || x0_logs),
+                "keep sample: null argument");
+    LDM_REQUIRE(nsteps >= 0, "keep sample: negative step count");
+    LDM_REQUIRE(S5 >= 0 && S6 >= 0, "keep sample: negative key count");
+    const bool guided = s5_base || s6_base || guide_scale;
+    if (guided) LDM_TRY(guided_args_ok(s, s5_base, s6_base, guide_scale, S5, S6));
+    else LDM_REQUIRE(!key_bias5_base && !key_bias6_base, "keep sample: base key biases without a base style");
+    const bool any = z0 || n0 || keep || keep_coef;
+    LDM_REQUIRE(!any || (z0 && n0 && keep && keep_coef), "keep sample: z0, n0, keep and keep_coef go together (one is NULL)");
+    if (nsteps == 0) return 0;
+    if (any)
+        LDM_TRY(workspace_extent_ok(ldm_ddim_workspace_floats_keep(s, w, nsteps, S5, S6, guided), "ldm_ddim_workspace_floats_keep",
+                                    workspace, stream));
+    else if (guided) LDM_TRY(guided_workspace_ok(s, w, nsteps, S5, S6, workspace, stream));
+    const Guide g{s5_base, s6_base, key_bias5_base, key_bias6_base, guide_scale};
+    const Keep k{z0, n0, keep, keep_coef};
+    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, eta, x0_logs, eps_logs, log_step_stride, workspace,
+                       stream, msolver, S5, S6, key_bias5, key_bias6, guided ? &g : nullptr, any ? &k : nullptr);
+}
+
+extern "C" int ldm_ddim_sample_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                                    const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
+                                    const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
+                                    const float* key_bias6_base, const float* guide_scale, const float* z0,
+                                    const float* n0, const float* keep, const float* keep_coef, const int64_t* t_table,
+                                    const float* coef_table, int32_t nsteps, float eta, float* x0_logs, float* eps_logs,
+                                    int64_t log_step_stride, float* workspace, void* stream) {
+    return keep_sample(s, w, x, s5, s6, s5_base, s6_base, S5, S6, key_bias5, key_bias6, key_bias5_base, key_bias6_base,
+                       guide_scale, z0, n0, keep, keep_coef, t_table, coef_table, nsteps, eta, x0_logs, eps_logs,
+                       log_step_stride, workspace, stream, false);
+}
+
+extern "C" int ldm_msolver_sample_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
+                                       const float* s6, const float* s5_base, const float* s6_base, int32_t S5,
+                                       int32_t S6, const float* key_bias5, const float* key_bias6,
+                                       const float* key_bias5_base, const float* key_bias6_base,
+                                       const float* guide_scale, const float* z0, const float* n0, const float* keep,
+                                       const float* keep_coef, const int64_t* t_table, const float* coef_table,
+                                       int32_t nsteps, float* x0_logs, float* eps_logs, int64_t log_step_stride,
+                                       float* workspace, void* stream) {
+    return keep_sample(s, w, x, s5, s6, s5_base, s6_base, S5, S6, key_bias5, key_bias6, key_bias5_base, key_bias6_base,
+                       guide_scale, z0, n0, keep, keep_coef, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs,
+                       log_step_stride, workspace, stream, true);
 }

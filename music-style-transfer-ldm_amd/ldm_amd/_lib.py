@@ -224,6 +224,16 @@ SIGNATURES = {
                                             c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_vp, c_fp,
                                             c_int32, c_fp, c_fp, c_int64, c_fp, c_vp]),
     "ldm_guide_eps": (c_int32, [c_fp, c_fp, c_fp, c_int64, c_int32, c_fp, c_vp]),
+    # regional keep: the guided entries' list plus z0, n0, keep, keep_coef
+    "ldm_ddim_workspace_floats_keep": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_int32,
+                                                 c_int32, c_int32, c_int32]),
+    "ldm_ddim_sample_keep": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
+                                       c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                       c_vp, c_fp, c_int32, c_float, c_fp, c_fp, c_int64, c_fp, c_vp]),
+    "ldm_msolver_sample_keep": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
+                                          c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                          c_fp, c_vp, c_fp, c_int32, c_fp, c_fp, c_int64, c_fp, c_vp]),
+    "ldm_keep_blend": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_int64, c_vp]),
     # backward / optimiser
     "ldm_conv_tiled_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),
     "ldm_conv_sconv_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),

@@ -38,11 +38,21 @@ def _mel_to_hz(m):
     return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
 
 
+def _mel_points(sr, n_mels):
+    """The n_mels + 2 corner frequencies in Hz of the filterbank's triangles (triangle m: points m, m + 1, m + 2)."""
+    return _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(sr / 2.0), n_mels + 2))
+
+
+def mel_centre_frequencies(sr=SR, n_mels=128):
+    """The centre frequency in Hz of each of mel_filterbank's n_mels triangles (float64 [n_mels], ascending)."""
+    return _mel_points(sr, n_mels)[1:-1].copy()
+
+
 @functools.lru_cache(maxsize=None)
 def mel_filterbank(sr=SR, n_fft=N_FFT, n_mels=128):
     """The Slaney mel filterbank [n_mels, n_fft/2 + 1] (fmin 0, fmax sr/2, area-normalised), float64, read-only."""
     fft_f = np.linspace(0.0, sr / 2.0, n_fft // 2 + 1)
-    mel_f = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(sr / 2.0), n_mels + 2))
+    mel_f = _mel_points(sr, n_mels)
     fdiff = np.diff(mel_f)
     ramps = mel_f[:, None] - fft_f[None, :]
     lower = -ramps[:-2] / fdiff[:-1, None]

@@ -194,13 +194,28 @@ class UNetEngine:
         self._bound[skey] = (vkey, w)
         return w
 
-    def workspace(self, shape, device, nsteps=0, slot=0, keys=None, guided=False, plan_batch=None):
+    def workspace(self, shape, device, nsteps=0, slot=0, keys=None, guided=False, plan_batch=None, keep=False):
         """Workspace for this shape and its bound plans; `slot` separates concurrently running sub-batch
         chains.  Zero-filled on allocation: it carries the split-K tile counters (ldm_capi.h).
         keys = (S5, S6): the style-mixing loops' workspace for those key counts (a buffer of its own).
         guided: the guided loops' workspace for the caller's `shape` (sized by the guided function for the doubled
         batch the body runs at; a buffer of its own; keys (0, 0) = the maps' own counts; plan_batch as in
-        _guided_weights)."""
+        _guided_weights).
+        keep: the regional-keep loops' workspace (ldm_ddim_workspace_floats_keep), guided or not; a buffer of its own."""
+        if keep:
+            w = self._guided_weights(shape.B, shape.C, shape.H, shape.W, plan_batch) if guided else self.weights(shape)
+            keys = tuple(keys) if keys else (0, 0)
+            n = L.load().ldm_ddim_workspace_floats_keep(byref(shape), byref(w), int(nsteps), int(keys[0]), int(keys[1]),
+                                                        1 if guided else 0)
+            if n <= 0:
+                raise RuntimeError("ldm_ddim_workspace_floats_keep failed")
+            key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot, "keep", bool(guided),
+                   plan_batch or 0) + keys
+            ws = self._ws.get(key)
+            if ws is None or ws.numel() < n:
+                ws = torch.zeros(int(n), device=device, dtype=torch.float32)
+                self._ws[key] = ws
+            return ws
         if guided:
             w = self._guided_weights(shape.B, shape.C, shape.H, shape.W, plan_batch)
             keys = tuple(keys) if keys else (0, 0)
@@ -353,13 +368,43 @@ class UNetEngine:
                 return wf
         return self.weights(self.shape(2 * B, C, H, W))
 
-    def _guided_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5,
-                     key_bias6, base, scale, plan_batch=None):
-        """One guided C loop (ldm_*_sample_guided): base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the
-        target's key counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights."""
+    class KeepOperands(tuple):
+        """(z0, n0, w, coefs) as keep_operands() returns them: checked, contiguous fp32 on the device."""
+
+    @classmethod
+    def keep_operands(cls, keep, xshape, n, device):
+        """The regional keep's operands checked and made contiguous fp32 on `device`: keep is a dict or tuple of z0, n0
+        ([B,C,H,W] like x), w ([B,H,W] keep weights: 1 keeps the content, 0 is free) and coefs ([n,2],
+        ForwardDiffusion.keep_coefs).  ValueError for wrong shapes and for a w that is not finite or lies outside
+        [0, 1].  A KeepOperands is returned as it is (a captured loop's static buffers)."""
+        if isinstance(keep, cls.KeepOperands):
+            return keep
+        if isinstance(keep, dict):
+            try:
+                keep = (keep["z0"], keep["n0"], keep["w"], keep["coefs"])
+            except KeyError as e:
+                raise ValueError(f"keep: missing entry {e} (need z0, n0, w, coefs)") from None
+        if len(keep) != 4 or any(not isinstance(v, torch.Tensor) for v in keep):
+            raise ValueError("keep must hold the four tensors z0, n0, w, coefs")
+        z0, n0, w, coefs = keep
+        B, C, H, W = xshape
+        if tuple(z0.shape) != tuple(xshape) or tuple(n0.shape) != tuple(xshape):
+            raise ValueError(f"keep: z0 / n0 must be shaped like x {tuple(xshape)}, got {tuple(z0.shape)}, {tuple(n0.shape)}")
+        if tuple(w.shape) != (B, H, W):
+            raise ValueError(f"keep: w must be [B,H,W] = {(B, H, W)}, got {tuple(w.shape)}")
+        if tuple(coefs.shape) != (n, 2):
+            raise ValueError(f"keep: coefs must be [n,2] for n = {n} steps, got {tuple(coefs.shape)}")
+        wf = w.detach().to(torch.float32)
+        if not bool(torch.isfinite(wf).all()):
+            raise ValueError("keep: w must be finite (NaN / inf given)")
+        if not (bool((wf >= 0).all()) and bool((wf <= 1).all())):
+            raise ValueError("keep: w must lie in [0, 1]")
+        return cls.KeepOperands(v.detach().to(device, torch.float32).contiguous() for v in (z0, n0, wf, coefs))
+
+    def _guided_operands(self, x, s5, s6, key_bias5, key_bias6, base, scale):
+        """The guided C entries' operands checked: (S5, S6, (s5_base, s6_base, S5, S6, key_bias5, key_bias6,
+        key_bias5_base, key_bias6_base, scale) as pointers)."""
         B, C, H, W = x.shape
-        shape = self.shape(B, C, H, W)
-        n = t_table.shape[0]
         s5b, s6b, kb5b, kb6b = base
         ops.require_device(s5b, s6b, scale, what="guidance operand")
         if tuple(s5b.shape) != tuple(s5.shape) or tuple(s6b.shape) != tuple(s6.shape):
@@ -374,13 +419,57 @@ class UNetEngine:
         if S5:
             S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
             _, _, p5b, p6b = self._mix_check(x, s5b, s6b, kb5b, kb6b)
-        elif tuple(s5.shape) != (B, 256, H // 4, W // 4) or tuple(s6.shape) != (B, 512, H // 8, W // 8):
+        else:
+            self._single_maps_check(x, s5, s6)
+        return S5, S6, (s5b.data_ptr(), s6b.data_ptr(), S5, S6, p5, p6, p5b, p6b, scale.data_ptr())
+
+    @staticmethod
+    def _single_maps_check(x, s5, s6):
+        B, C, H, W = x.shape
+        if tuple(s5.shape) != (B, 256, H // 4, W // 4) or tuple(s6.shape) != (B, 512, H // 8, W // 8):
             raise RuntimeError(f"UNet: style maps must be s5 [B,256,H/4,W/4], s6 [B,512,H/8,W/8] for z {tuple(x.shape)}; "
                                f"got {tuple(s5.shape)}, {tuple(s6.shape)}")
+
+    def _keep_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5,
+                   key_bias6, base, scale, plan_batch, kp):
+        """One C loop with the regional keep (ldm_*_sample_keep), guided (base / scale as in _guided_call) or not."""
+        B, C, H, W = x.shape
+        shape = self.shape(B, C, H, W)
+        n = t_table.shape[0]
+        guided = base is not None
+        if guided:
+            S5, S6, gargs = self._guided_operands(x, s5, s6, key_bias5, key_bias6, base, scale)
+            w = self._guided_weights(B, C, H, W, plan_batch)
+        else:
+            S5, S6, p5, p6 = 0, 0, None, None
+            if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
+                S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
+            else:
+                self._single_maps_check(x, s5, s6)
+            w = self.weights(shape)
+            gargs = (None, None, S5, S6, p5, p6, None, None, None)
+        kp = self.keep_operands(kp, x.shape, n, x.device)
+        ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6), guided=guided, plan_batch=plan_batch, keep=True)
+        head = (byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr()) + gargs + \
+            tuple(v.data_ptr() for v in kp) + (t_table.data_ptr(), coef_table.data_ptr(), n)
+        tail = (ops._p(eps_logs), int(log_stride), ws.data_ptr(), ops.stream_handle())
+        if solver == "msolver":
+            L.call("ldm_msolver_sample_keep", *head, x0_logs.data_ptr(), *tail)
+        else:
+            L.call("ldm_ddim_sample_keep", *head, float(eta), ops._p(x0_logs), *tail)
+
+    def _guided_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5,
+                     key_bias6, base, scale, plan_batch=None):
+        """One guided C loop (ldm_*_sample_guided): base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the
+        target's key counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights."""
+        B, C, H, W = x.shape
+        shape = self.shape(B, C, H, W)
+        n = t_table.shape[0]
+        S5, S6, gargs = self._guided_operands(x, s5, s6, key_bias5, key_bias6, base, scale)
         w = self._guided_weights(B, C, H, W, plan_batch)   # the body runs at the doubled batch: targets, then bases
         ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6), guided=True, plan_batch=plan_batch)
-        head = (byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(), s5b.data_ptr(), s6b.data_ptr(), S5, S6,
-                p5, p6, p5b, p6b, scale.data_ptr(), t_table.data_ptr(), coef_table.data_ptr(), n)
+        head = (byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr()) + gargs + \
+            (t_table.data_ptr(), coef_table.data_ptr(), n)
         tail = (ops._p(eps_logs), int(log_stride), ws.data_ptr(), ops.stream_handle())
         if solver == "msolver":
             L.call("ldm_msolver_sample_guided", *head, x0_logs.data_ptr(), *tail)
@@ -388,7 +477,10 @@ class UNetEngine:
             L.call("ldm_ddim_sample_guided", *head, float(eta), ops._p(x0_logs), *tail)
 
     def _ddim_call(self, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5=None,
-                   key_bias6=None, base=None, scale=None, plan_batch=None):
+                   key_bias6=None, base=None, scale=None, plan_batch=None, kp=None):
+        if kp is not None:
+            return self._keep_call("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
+                                   key_bias5, key_bias6, base, scale, plan_batch, kp)
         if base is not None:
             return self._guided_call("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
                                      key_bias5, key_bias6, base, scale, plan_batch)
@@ -410,7 +502,10 @@ class UNetEngine:
                int(log_stride), ws.data_ptr(), ops.stream_handle())
 
     def _msolver_call(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs, log_stride, slot, key_bias5=None,
-                      key_bias6=None, base=None, scale=None, plan_batch=None):
+                      key_bias6=None, base=None, scale=None, plan_batch=None, kp=None):
+        if kp is not None:
+            return self._keep_call("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, log_stride, slot,
+                                   key_bias5, key_bias6, base, scale, plan_batch, kp)
         if base is not None:
             return self._guided_call("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, log_stride, slot,
                                      key_bias5, key_bias6, base, scale, plan_batch)
@@ -432,22 +527,23 @@ class UNetEngine:
                ws.data_ptr(), ops.stream_handle())
 
     def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None, key_bias5=None,
-                     key_bias6=None, base=None, guidance_scale=1.0):
+                     key_bias6=None, base=None, guidance_scale=1.0, keep=None):
         """ddim_loop's twin for the multistep solver (DPM-Solver++(2M) or its first-order form): coef_table
         [n,8] from ForwardDiffusion.multistep_coefs (device), no eta.  x0_logs [n,B,C,H,W] is required: step i
-        reads step i-1's slot as its history.  Same sub-batch chains, base= and guidance_scale= as ddim_loop."""
+        reads step i-1's slot as its history.  Same sub-batch chains, base=, guidance_scale= and keep= as ddim_loop."""
         if x0_logs is None:
             raise ValueError("msolver_loop: x0_logs is required (it is the solver's history)")
         if coef_table.dim() != 2 or coef_table.shape[1] != 8 or coef_table.shape[0] != t_table.shape[0]:
             raise ValueError(f"msolver_loop: coef_table must be [n,8] for n = {t_table.shape[0]} steps, "
                              f"got {tuple(coef_table.shape)}")
         return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
-                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None, base=None, scale=None, pb=None:
-                          self._msolver_call(xs, a5, a6, t, coef_table, x0l, epl, stride, slot, b5, b6, base, scale, pb),
-                          key_bias5, key_bias6, base, guidance_scale)
+                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None, base=None, scale=None, pb=None,
+                          kp=None:
+                          self._msolver_call(xs, a5, a6, t, coef_table, x0l, epl, stride, slot, b5, b6, base, scale, pb, kp),
+                          key_bias5, key_bias6, base, guidance_scale, keep)
 
     def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None,
-                  key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0):
+                  key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None):
         """In-place reverse loop on x ([B,C,H,W] contiguous fp32).  t_table [n,B] int64, coef [n,4] (device).
 
         Style mixing: s5 / s6 may hold R style references stacked along the map's height (s5 [B,256,R*H/4,W/4],
@@ -461,24 +557,34 @@ class UNetEngine:
         call is the unguided one, argument for argument (a scale other than 1 then has nothing to guide against:
         ValueError).
 
+        Regional keep: keep = a dict or tuple of z0, n0 ([B,C,H,W]: the clean latent and the q_sample noise), w
+        ([B,H,W] in [0,1]: 1 keeps the content, 0 is free) and coefs ([n,2], ForwardDiffusion.keep_coefs).  After every
+        step's update the state becomes (1 - w) x + w (coefs[i][0] z0 + coefs[i][1] n0), fused into dec1's epilogue;
+        the logs stay the model's own prediction.  Composes with the mix, the guidance and the split (each chain gets
+        its slice).  ValueError for a w outside [0, 1] or not finite, and for wrong shapes.
+
         split > 1 runs the batch as that many independent sub-batch chains, each on its own stream
         (forked from and joined back into the current stream, so it also works under graph capture).
         The path is per-sample, so the result is the same up to fp32 summation order (a sub-batch
         size may get a conv plan that splits K differently); the chains' launch and memory latencies
         overlap each other's work."""
         return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
-                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None, base=None, scale=None, pb=None:
-                          self._ddim_call(xs, a5, a6, t, coef_table, eta, x0l, epl, stride, slot, b5, b6, base, scale, pb),
-                          key_bias5, key_bias6, base, guidance_scale)
+                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None, base=None, scale=None, pb=None,
+                          kp=None:
+                          self._ddim_call(xs, a5, a6, t, coef_table, eta, x0l, epl, stride, slot, b5, b6, base, scale, pb, kp),
+                          key_bias5, key_bias6, base, guidance_scale, keep)
 
     def _loop(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5=None, key_bias6=None, base=None,
-              guidance_scale=1.0):
+              guidance_scale=1.0, keep=None):
         """The whole batch in one C call, or one per sub-batch chain; call(x, s5, s6, t, x0_logs, eps_logs,
-        log_stride, slot[, key_bias5, key_bias6[, base, scale]]) is one sampler's C call."""
+        log_stride, slot[, key_bias5, key_bias6[, base, scale, plan_batch, keep]]) is one sampler's C call.  The keep
+        operands are sliced with the batch."""
         B = x.shape[0]
+        if keep is not None:
+            keep = self.keep_operands(keep, x.shape, t_table.shape[0], x.device)
         if base is not None:
             return self._loop_guided(x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5, key_bias6,
-                                     base, guidance_scale)
+                                     base, guidance_scale, keep)
         if not self.is_unguided(None, guidance_scale):
             raise ValueError("guidance_scale other than 1 needs a base style to guide against (base=)")
         keys = self.mix_keys(x, s5, s6, key_bias5, key_bias6)
@@ -487,7 +593,9 @@ class UNetEngine:
         if plan is None:
             plan = self.split_plan(t_table, B, split) if split > 1 else None
         if not plan or len(plan) == 1:
-            if keys is None:
+            if keep is not None:
+                call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6, None, None, None, keep)
+            elif keys is None:
                 call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0)
             else:
                 call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6)
@@ -499,7 +607,7 @@ class UNetEngine:
         for k, (lo, hi, t_sub) in enumerate(plan):   # bind / pack / allocate on the main stream first
             shape = self.shape(hi - lo, C, H, W)
             self.weights(shape)
-            self.workspace(shape, x.device, t_table.shape[0], k, keys=keys)
+            self.workspace(shape, x.device, t_table.shape[0], k, keys=keys, keep=keep is not None)
         for k, (lo, hi, t_sub) in enumerate(plan):
             st = streams[k]
             st.wait_stream(main)
@@ -508,7 +616,11 @@ class UNetEngine:
             with torch.cuda.stream(st):
                 x0l = None if x0_logs is None else x0_logs[0, lo:hi]
                 epl = None if eps_logs is None else eps_logs[0, lo:hi]
-                if keys is None:
+                if keep is not None:
+                    call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, x0l, epl, per_step, k,
+                         None if key_bias5 is None else key_bias5[lo:hi], None if key_bias6 is None else key_bias6[lo:hi],
+                         None, None, None, self._keep_cut(keep, lo, hi))
+                elif keys is None:
                     call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, x0l, epl, per_step, k)
                 else:   # the biases are split with the maps (leading-dimension slices stay contiguous)
                     call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, x0l, epl, per_step, k,
@@ -519,7 +631,13 @@ class UNetEngine:
         return x
 
 
-    def _loop_guided(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5, key_bias6, base, scale):
+    @classmethod
+    def _keep_cut(cls, kp, lo, hi):
+        """A sub-batch chain's slice of the keep operands (the coefficient table is shared)."""
+        return None if kp is None else cls.KeepOperands((kp[0][lo:hi], kp[1][lo:hi], kp[2][lo:hi], kp[3]))
+
+    def _loop_guided(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5, key_bias6, base, scale,
+                     kp=None):
         """_loop for a guided sampler: the base maps, their biases and the scales are sliced with the batch.  On the
         step-kernel path the sub-batch chains run the whole batch's plans (_guided_weights), so split > 1 gives each
         sample bitwise what split = 1 gives it while both select the same per-batch forms (the bottleneck value
@@ -534,7 +652,7 @@ class UNetEngine:
         if plan is None:
             plan = self.split_plan(t_table, B, split) if split > 1 else None
         if not plan or len(plan) == 1:
-            call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6, base, scale)
+            call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6, base, scale, None, kp)
             return x
         per_step = x[0].numel() * B
         main = torch.cuda.current_stream(x.device)
@@ -543,7 +661,7 @@ class UNetEngine:
         keys = self._guided_keys(x, s5, s6, key_bias5, key_bias6, base)
         for k, (lo, hi, t_sub) in enumerate(plan):   # bind / pack / allocate on the main stream first
             self.workspace(self.shape(hi - lo, C, H, W), x.device, t_table.shape[0], k, keys=keys, guided=True,
-                           plan_batch=B)
+                           plan_batch=B, keep=kp is not None)
 
         def cut(v, lo, hi):
             return None if v is None else v[lo:hi]
@@ -556,7 +674,8 @@ class UNetEngine:
             with torch.cuda.stream(st):
                 call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, None if x0_logs is None else x0_logs[0, lo:hi],
                      None if eps_logs is None else eps_logs[0, lo:hi], per_step, k, cut(key_bias5, lo, hi),
-                     cut(key_bias6, lo, hi), tuple(cut(v, lo, hi) for v in base), scale[lo:hi], B)
+                     cut(key_bias6, lo, hi), tuple(cut(v, lo, hi) for v in base), scale[lo:hi], B,
+                     self._keep_cut(kp, lo, hi))
         for st in streams:
             main.wait_stream(st)
         return x
@@ -566,12 +685,14 @@ class GraphedDDIM:
     """A captured reverse loop with static buffers: replay() re-runs all n steps from x_init."""
 
     def __init__(self, engine, x_init, s5, s6, t_table, coef_table, eta, logs=True, split=1, solver="ddim",
-                 key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0):
+                 key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None):
         """solver="ddim": coef_table [n,4] and eta, the reference's update; solver="msolver": coef_table [n,8]
         (ForwardDiffusion.multistep_coefs), eta unused and the x0 logs always kept (the solver's history).
         s5 / s6 may be stacked style references with key_bias5 / key_bias6 (UNetEngine.ddim_loop).
         base / guidance_scale: style guidance as in UNetEngine.ddim_loop; the strengths live in the static device
-        buffer `scale` ([B] fp32), which set_guidance_scale() rewrites between replays without a new capture."""
+        buffer `scale` ([B] fp32), which set_guidance_scale() rewrites between replays without a new capture.
+        keep: the regional keep as in UNetEngine.ddim_loop; its operands are cloned into static buffers, and
+        set_keep() rewrites the weights between replays without a new capture."""
         if solver not in ("ddim", "msolver"):
             raise ValueError(f"GraphedDDIM: unknown solver {solver!r}")
         self.solver = solver
@@ -594,6 +715,10 @@ class GraphedDDIM:
         self.t_table = t_table.to(dev).contiguous()
         self.coef = coef_table.to(dev).contiguous()
         n = self.t_table.shape[0]
+        self.keep = None
+        if keep is not None:
+            kp = engine.keep_operands(keep, x_init.shape, n, dev)
+            self.keep = engine.KeepOperands(v.clone() for v in kp)
         self.x0_logs = torch.empty((n,) + tuple(x_init.shape), device=dev) if logs else None
         self.eps_logs = torch.empty((n,) + tuple(x_init.shape), device=dev) if logs else None
         self.eta = float(eta)
@@ -626,16 +751,20 @@ class GraphedDDIM:
                 kb6 = None if self.kb6 is None else self.kb6[lo:hi]
                 gb = None if self.base is None else tuple(None if v is None else v[lo:hi] for v in self.base)
                 gs = None if self.scale is None else self.scale[lo:hi]
+                kc = engine._keep_cut(self.keep, lo, hi)
                 if solver == "msolver":
                     engine._msolver_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, x0l, epl,
-                                         per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None)
+                                         per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None, kc)
                 else:
                     engine._ddim_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
-                                      x0l, epl, per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None)
+                                      x0l, epl, per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None,
+                                      kc)
             self.graphs.append(g)
 
     def _run(self, plan=None):
         guide = {} if self.base is None else {"base": self.base, "guidance_scale": self.scale}
+        if self.keep is not None:
+            guide["keep"] = self.keep
         if self.solver == "msolver":
             self.engine.msolver_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.x0_logs, self.eps_logs,
                                      plan=plan, key_bias5=self.kb5, key_bias6=self.kb6, **guide)
@@ -649,6 +778,15 @@ class GraphedDDIM:
         if self.scale is None:
             raise ValueError("set_guidance_scale: this loop was captured without a base style")
         self.scale.copy_(self.engine.guidance_scale(guidance_scale, self.scale.shape[0]), non_blocking=False)
+
+    def set_keep(self, w):
+        """Writes new keep weights ([B,H,W] in [0,1]) into the static buffer the captured loop reads: the next replay
+        runs under the new mask.  Only for a graph captured with keep=."""
+        if self.keep is None:
+            raise ValueError("set_keep: this loop was captured without keep=")
+        kp = self.engine.keep_operands((self.keep[0], self.keep[1], w, self.keep[3]), self.x.shape, self.keep[3].shape[0],
+                                       self.x.device)
+        self.keep[2].copy_(kp[2], non_blocking=False)
 
     def replay(self):
         if self.streams is None:

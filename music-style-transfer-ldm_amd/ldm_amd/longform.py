@@ -6,7 +6,10 @@ overlap frames.  Each window is referred to its own maximum, exactly as the trai
 (audio.chunk_mel_images); the stitch undoes that per window and crossfades linearly in dB where two windows overlap.
 overlap <= frames / 2, so no frame lies in more than two windows.
 """
-from . import ops
+import numpy as np
+import torch
+
+from . import audio, ops
 
 
 def window_plan(T_total, frames=512, overlap=64):
@@ -38,3 +41,66 @@ def stitch_windows(y, ref_db, overlap, T_total, max_db=80, return_db=False):
     if y.shape[0] != N:
         raise ValueError(f"stitch_windows: {y.shape[0]} windows given, the plan of T_total {T_total} has {N}")
     return ops.mel_stitch(y, ref_db, overlap, T_total, max_db, return_db)
+
+
+def _keep_profile(n, lo, hi, feather):
+    """[n] float64: 1 on indices [lo, hi] (clipped to the axis), 0 elsewhere, with a linear ramp over the `feather`
+    outermost indices inside each edge, (d + 1) / (feather + 1) at distance d from the edge.  An edge that is the
+    axis' own end gets no ramp."""
+    p = np.zeros(n, dtype=np.float64)
+    lo, hi = max(int(lo), 0), min(int(hi), n - 1)
+    if hi < lo:
+        return p
+    idx = np.arange(lo, hi + 1)
+    w = np.ones(idx.shape[0], dtype=np.float64)
+    if feather > 0:
+        if lo > 0:
+            w = np.minimum(w, (idx - lo + 1) / (feather + 1.0))
+        if hi < n - 1:
+            w = np.minimum(w, (hi - idx + 1) / (feather + 1.0))
+    p[lo:hi + 1] = w
+    return p
+
+
+def keep_mask(T_total, n_mels=128, sr=audio.SR, times=(), bands=(), feather=0):
+    """The keep mask [n_mels, T_total] in [0, 1] (CPU fp32) of a recording of T_total mel frames: 1 where the content
+    is to stay as it is.  times: (t0, t1) spans in seconds, covering the frames whose time f * hop / sr lies in
+    [t0, t1]; bands: (f_lo, f_hi) in Hz, covering the mel bins whose centre frequency (audio.mel_centre_frequencies)
+    lies in [f_lo, f_hi].  feather: a linear ramp of that many frames (bins) inside each edge of a region, except at
+    the ends of the recording (of the mel axis).  The result is the union (max) of all regions; none gives zeros."""
+    T_total, n_mels, feather = int(T_total), int(n_mels), int(feather)
+    if T_total < 1 or n_mels < 1 or feather < 0:
+        raise ValueError(f"keep_mask: need T_total >= 1, n_mels >= 1, feather >= 0; got {T_total}, {n_mels}, {feather}")
+    hop = audio.N_FFT // 4
+    m = np.zeros((n_mels, T_total), dtype=np.float64)
+    ft = np.arange(T_total) * (hop / float(sr))
+    for t0, t1 in times:
+        if not t0 <= t1:
+            raise ValueError(f"keep_mask: a time span needs t0 <= t1, got ({t0}, {t1})")
+        inside = np.nonzero((ft >= t0) & (ft <= t1))[0]
+        if inside.size:
+            m = np.maximum(m, _keep_profile(T_total, inside[0], inside[-1], feather)[None, :])
+    fc = audio.mel_centre_frequencies(sr, n_mels)
+    for f0, f1 in bands:
+        if not f0 <= f1:
+            raise ValueError(f"keep_mask: a band needs f_lo <= f_hi, got ({f0}, {f1})")
+        inside = np.nonzero((fc >= f0) & (fc <= f1))[0]
+        if inside.size:
+            m = np.maximum(m, _keep_profile(n_mels, inside[0], inside[-1], feather)[:, None])
+    return torch.from_numpy(m.astype(np.float32))
+
+
+def mask_windows(mask, frames=512, overlap=64):
+    """A keep mask [n_mels, T_total] cut by window_plan exactly as the content is cut: [N, 1, n_mels, frames], window n
+    holding frames [n * stride, n * stride + frames); frames at or beyond T_total (a padded tail) get 0."""
+    if mask.dim() != 2:
+        raise ValueError(f"mask_windows: the mask must be [n_mels, T_total], got {tuple(mask.shape)}")
+    n_mels, T_total = mask.shape
+    N, stride = window_plan(T_total, frames, overlap)
+    out = torch.zeros((N, 1, n_mels, frames), dtype=mask.dtype, device=mask.device)
+    for n in range(N):
+        t0 = n * stride
+        t1 = min(t0 + frames, T_total)
+        if t1 > t0:
+            out[n, 0, :, :t1 - t0] = mask[:, t0:t1]
+    return out

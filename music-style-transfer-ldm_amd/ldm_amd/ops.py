@@ -988,6 +988,23 @@ def msolver_step_(x, eps, coef8, x0_log, x0_prev=None, eps_log=None):
     return x
 
 
+def keep_blend_(x, z0, n0, keep, coef):
+    """The regional keep on whole tensors, in place on x (ldm_keep_blend): x = (1 - w) x + w (a z0 + b n0) per element
+    in fp32, one rounding per operation.  x / z0 / n0 [B,C,H,W] contiguous fp32, keep [B,H,W] fp32 (shared by the
+    channels), coef a device fp32 row {a, b}."""
+    require_device(x, z0, n0, keep, coef)
+    B, C, H, W = x.shape
+    if z0.shape != x.shape or n0.shape != x.shape or tuple(keep.shape) != (B, H, W) or coef.numel() != 2:
+        raise ValueError(f"keep_blend: z0 / n0 must be shaped like x {tuple(x.shape)}, keep [B,H,W] and coef hold two "
+                         f"values; got {tuple(z0.shape)}, {tuple(n0.shape)}, {tuple(keep.shape)}, {tuple(coef.shape)}")
+    for t in (x, z0, n0, keep, coef):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("keep_blend: operands must be contiguous fp32 tensors")
+    L.call("ldm_keep_blend", x.data_ptr(), z0.data_ptr(), n0.data_ptr(), keep.data_ptr(), coef.data_ptr(), B, C, H * W,
+           stream_handle())
+    return x
+
+
 def guide_eps(e_t, e_b, scale, out=None):
     """Style guidance on whole noise predictions (ldm_guide_eps): e_b + scale[b] * (e_t - e_b) per element in fp32,
     one rounding per operation.  e_t / e_b [B, ...] contiguous fp32, scale a device fp32 [B] tensor."""

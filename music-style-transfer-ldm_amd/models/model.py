@@ -188,6 +188,16 @@ class ForwardDiffusion(nn.Module):
         a_t, a_n = ab[times[:-1]], ab[times[1:]]
         return torch.stack([torch.sqrt(a_t), torch.sqrt(1 - a_t), torch.sqrt(a_n), torch.sqrt(1 - a_n)], 1).contiguous()
 
+    def keep_coefs(self, times, exact_last=True):
+        """fp32 [n,2] {sqrt(ab_next), sqrt(1-ab_next)} for consecutive `times` (columns 2 and 3 of reverse_coefs): where
+        the content's own noising trajectory a z0 + b noise stands after step i, for every solver (the regional keep,
+        keep_blend).  exact_last: the last row is (1, 0), so a fully kept pixel ends as z0 itself and not as z0 at
+        the last index's noise level."""
+        c = self.reverse_coefs(times)[:, 2:4].contiguous()
+        if exact_last and c.shape[0]:
+            c[-1, 0], c[-1, 1] = 1.0, 0.0
+        return c
+
     def multistep_coefs(self, times, order=2):
         """fp32 [n,8] rows {alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0} of the multistep solver (DPM-Solver++ in its
         data-prediction form) for consecutive `times`, n = len(times) - 1:
@@ -420,14 +430,17 @@ class LDM(nn.Module):
         }
 
     # -------------------------------------------------------------------------------------------
-    def _reverse(self, z_t, style_embedding, times, eta, order=0, base_embedding=None, guidance_scale=1.0):
+    def _reverse(self, z_t, style_embedding, times, eta, order=0, base_embedding=None, guidance_scale=1.0, keep=None):
         """The shared body of the samplers: len(times)-1 UNet + update steps in one C call.  order 0: the
         reference's DDIM-style update with eta; 1 / 2: the multistep solver of that order (eta unused).
 
         base_embedding / guidance_scale (a finite float or one per sample, [B]): style guidance.  Each step
         evaluates the denoiser under both embeddings on the same x and t and steps on eps = e_b + s (e_t - e_b)
         (fp32, one rounding per operation); the logs hold the guided x0 / eps.  Without a base and at scale 1 the
-        calls below are the unguided ones, argument for argument."""
+        calls below are the unguided ones, argument for argument.
+
+        keep = (z0, n0, w, coefs): the regional keep (UNetEngine.ddim_loop).  After each step's update the state is
+        blended with coefs[i][0] z0 + coefs[i][1] n0 under the weights w [B,H,W]; the logs stay unblended."""
         guided = not UNetEngine.is_unguided(base_embedding, guidance_scale)
         if guided:      # the checks, before anything runs
             if base_embedding is None:
@@ -442,6 +455,8 @@ class LDM(nn.Module):
                         "repeats a single style for a mix of R references)")
         n = int(times.numel()) - 1
         logs = {"timesteps": [], "pred_x0": [], "noise_pred": []}
+        if keep is not None:
+            keep = UNetEngine.keep_operands(keep, z_t.shape, max(n, 0), z_t.device)   # ValueError on a bad mask
         if n <= 0:
             return z_t, logs
         if order:
@@ -466,8 +481,10 @@ class LDM(nn.Module):
             scale = scale.to(dev)
             mix = mix or base[2] is not None or base[3] is not None
             guide = {"base": base, "guidance_scale": scale}
+        if keep is not None:
+            guide["keep"] = keep
         with torch.no_grad():
-            if UNetEngine.supports(x.shape[1]) and (mix or guided):
+            if UNetEngine.supports(x.shape[1]) and (mix or guided or keep is not None):
                 eng = engine_for(self.unet)
                 if order:
                     eng.msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs, key_bias5=kb5, key_bias6=kb6, **guide)
@@ -494,6 +511,8 @@ class LDM(nn.Module):
                                           eps_logs[i])
                     else:
                         ops.ddim_step_(x, eps, coefs[i].contiguous(), float(eta), x0_logs[i], eps_logs[i])
+                    if keep is not None:    # the stand-alone blend, after the update kernel
+                        ops.keep_blend_(x, keep[0], keep[1], keep[2], keep[3][i])
         logs["timesteps"] = [int(v) for v in times[:-1]]
         logs["pred_x0"] = list(x0_logs.unbind(0))
         logs["noise_pred"] = list(eps_logs.unbind(0))
@@ -620,13 +639,29 @@ class LDM(nn.Module):
                              f"{steps}, t_start {t_start} (with more steps than indices two times coincide)")
         return torch.linspace(t_start, 0, steps + 1).long()
 
-    def _solve(self, z_t, style_embedding, times, solver, eta, base_embedding=None, guidance_scale=1.0):
+    def _solve(self, z_t, style_embedding, times, solver, eta, base_embedding=None, guidance_scale=1.0, keep=None):
         if solver not in self._SOLVERS:
             raise ValueError(f"unknown solver {solver!r}: one of {sorted(self._SOLVERS)}")
-        return self._reverse(z_t, style_embedding, times, eta, self._SOLVERS[solver], base_embedding, guidance_scale)
+        return self._reverse(z_t, style_embedding, times, eta, self._SOLVERS[solver], base_embedding, guidance_scale,
+                             keep)
+
+    @staticmethod
+    def latent_keep(mask):
+        """A keep mask at spectrogram resolution [B,1,n_mels,F] reduced to latent resolution [B,H,W] = [B,n_mels/8,F/8]
+        by the mean over each 8 x 8 cell (the VAE's downsampling factor)."""
+        if mask.dim() != 4 or mask.shape[1] != 1 or mask.shape[2] % 8 or mask.shape[3] % 8:
+            raise ValueError(f"latent_keep: the mask must be [B,1,n_mels,F] with n_mels and F multiples of 8, got "
+                             f"{tuple(mask.shape)}")
+        B, _, M, F = mask.shape
+        return mask.float().reshape(B, M // 8, 8, F // 8, 8).mean(dim=(2, 4))
+
+    def _keep_tuple(self, keep, z0, noise, times, exact_last):
+        if z0 is None or noise is None:
+            raise ValueError("keep needs z0 and noise: the clean latent and the q_sample noise that produced z_t")
+        return (z0, noise, keep, self.noise_scheduler.keep_coefs(times, exact_last))
 
     def style_conditioned_sample(self, z_t, style_embedding, steps=20, solver="dpmpp2m", t_start=None, eta=0.0,
-                                 guidance_scale=1.0, base_embedding=None):
+                                 guidance_scale=1.0, base_embedding=None, keep=None, z0=None, noise=None, exact_last=True):
         """z_t at index t_start (default num_timesteps - 1) denoised in `steps` UNet passes over
         sample_times(t_start, steps).  solver: "dpmpp2m" (DPM-Solver++(2M), first-order first and last step),
         "dpmpp1" (its first-order form) or "ddim" (the reference's update, with eta, on this time grid).
@@ -635,13 +670,19 @@ class LDM(nn.Module):
         base_embedding (a style embedding with the target's key counts) and guidance_scale (a finite float or [B]):
         every step steers the noise prediction from the base style towards the target, e_b + s (e_t - e_b): s = 1
         samples the target, s > 1 exaggerates it, 0 < s < 1 applies it partly.  A scale other than 1 without a
-        base raises ValueError; scale 1 without a base is the unguided sampler."""
+        base raises ValueError; scale 1 without a base is the unguided sampler.
+
+        keep [B,H,W] in [0,1] with z0 and noise (z_t = q_sample(z0, t_start, noise)): the regional keep.  Where keep is
+        1 the state is held on the content's own noising trajectory and ends as z0 (exact_last) or as z0 at index
+        0's noise level; where it is 0 the sampler runs free; values between blend the two after every step."""
         t_start = self.num_timesteps - 1 if t_start is None else t_start
-        return self._solve(z_t, style_embedding, self.sample_times(t_start, steps), solver, eta, base_embedding,
-                           guidance_scale)
+        times = self.sample_times(t_start, steps)
+        kp = None if keep is None else self._keep_tuple(keep, z0, noise, times, exact_last)
+        return self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp)
 
     def content_style_transfer(self, content_spec, style_spec, t_start=99, steps=10, solver="dpmpp2m", noise=None,
-                               eta=0.0, style_weights=None, guidance_scale=1.0, base_style=None):
+                               eta=0.0, style_weights=None, guidance_scale=1.0, base_style=None, keep=None,
+                               composite=True):
         """Encode content, q_sample it at index t_start (the strength), denoise over sample_times(t_start, steps)
         with `solver`, decode.  Returns (decoded, z_t_decoded) like content_style_transfer_wrapper.
 
@@ -655,18 +696,44 @@ class LDM(nn.Module):
         guidance_scale / base_style: style guidance (style_conditioned_sample).  base_style is a spectrogram
         [B,1,n_mels,F] passed through the style encoder; None with a scale other than 1 takes the content
         spectrogram itself ("away from how it sounds now, towards the target").  Against a mix of R references the
-        base is tiled R times (tile_embedding)."""
+        base is tiled R times (tile_embedding).
+
+        keep: a mask in [0,1] of what to leave as it is, [B,1,n_mels,F] at spectrogram resolution (reduced by
+        latent_keep) or [B,H,W] at latent resolution: the regional keep with this call's own z_0 and noise.  composite
+        (spectrogram-resolution masks): the decoded window becomes (1 - M) decoded + M content_spec, since the VAE is
+        lossy and a kept region should come back as it went in."""
         if style_weights is not None and style_spec.dim() != 5:
             raise ValueError("style_weights needs a 5-D style_spec [B,R,1,n_mels,F]")
         content_spec = content_spec.float()
         style_spec = style_spec.float()
         times = self.sample_times(t_start, steps)
+        mask = None
+        if keep is not None:      # the checks, before anything runs
+            B = content_spec.shape[0]
+            if keep.dim() == 4:
+                if tuple(keep.shape) != (B, 1) + tuple(content_spec.shape[2:]):
+                    raise ValueError(f"keep: a spectrogram-resolution mask must be [B,1,n_mels,F] like the content "
+                                     f"{tuple(content_spec.shape)}, got {tuple(keep.shape)}")
+            elif tuple(keep.shape) != (B, content_spec.shape[2] // 8, content_spec.shape[3] // 8):
+                raise ValueError(f"keep: a latent-resolution mask must be [B,H,W] = [B,n_mels/8,F/8] for the content "
+                                 f"{tuple(content_spec.shape)}, got {tuple(keep.shape)}")
+            keep = keep.detach().to(content_spec.device, torch.float32)
+            if not bool(torch.isfinite(keep).all()):
+                raise ValueError("keep: the mask must be finite (NaN / inf given)")
+            if not (bool((keep >= 0).all()) and bool((keep <= 1).all())):
+                raise ValueError("keep: mask values must lie in [0, 1]")
+            if keep.dim() == 4:
+                mask, keep = keep, self.latent_keep(keep)
         z_0 = self.encoder(content_spec)
         t = torch.full((content_spec.shape[0],), int(t_start), dtype=torch.long)
         z_t, noise = self.noise_scheduler(z_0, t.to(content_spec.device), noise=noise)
+        kp = None
+        if keep is not None:
+            kp = UNetEngine.keep_operands(self._keep_tuple(keep, z_0, noise, times, True), z_t.shape, len(times) - 1,
+                                          z_t.device)
         style_embedding = self._style_embedding(style_spec, style_weights)
         if UNetEngine.is_unguided(base_style, guidance_scale):
-            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta)
+            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, keep=kp)
         else:
             UNetEngine.guidance_scale(guidance_scale, content_spec.shape[0])   # (validated before anything runs)
             base_spec = content_spec if base_style is None else base_style.float()
@@ -674,7 +741,9 @@ class LDM(nn.Module):
             R = int(style_embedding.get("refs", 1)) if isinstance(style_embedding, dict) else 1
             if R > 1:
                 base_embedding = self.tile_embedding(base_embedding, R)
-            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale)
+            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp)
         decoded = self.decoder(sampled, rescale=True)
+        if mask is not None and composite:
+            decoded = (1 - mask) * decoded + mask * content_spec
         z_t_decoded = self.decoder(z_t)
         return decoded, z_t_decoded

@@ -5,6 +5,7 @@ are crossfaded into one mel spectrogram that is vocoded once, so the phase is co
     python -m models.transfer --content a.wav --style b.wav --out c.wav [--checkpoint ldm.pth]
     python -m models.transfer --content a.wav --style b.wav c.wav --style-weights 0.7 0.3 --style-refs 2 --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --guidance-scale 2.5 --out o.wav
+    python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --keep-band 0:200 --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
 """
@@ -33,7 +34,8 @@ def style_window_indices(Ns, refs):
 
 def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, num_timesteps=100, eta=0.0,
                        batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None,
-                       style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None):
+                       style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None, keep=None,
+                       composite=True):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -58,8 +60,23 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     Style guidance (needs a solver): guidance_scale s (a finite float) steers every step from a base style towards
     the target, e_b + s (e_t - e_b) (LDM.content_style_transfer): s > 1 exaggerates the style, 0 < s < 1 applies
     it partly.  base_style "content" (the default when s is not 1) takes each window's own content mel as the
-    base; a waveform [L] is windowed and paired like `style`.  s = 1 without a base_style is the unguided call."""
+    base; a waveform [L] is windowed and paired like `style`.  s = 1 without a base_style is the unguided call.
+
+    Regional transfer (needs a solver): keep is a mask [n_mels, T_total] in [0, 1] (longform.keep_mask) of what stays
+    as it is.  It is cut into windows like the content (longform.mask_windows) and every window's sampler holds the
+    kept region on the content's own noising trajectory (LDM.content_style_transfer); with composite the kept region
+    of every decoded window is the content window itself.  Composes with mixing and guidance."""
     n_mels = 128
+    if keep is not None:
+        if solver is None:
+            raise ValueError("transfer_recording: keep needs a solver (the reference's sampler has no regional keep)")
+        keep = torch.as_tensor(keep, dtype=torch.float32)
+        T_keep = 1 + content.numel() // HOP if content.dim() == 1 else -1
+        if tuple(keep.shape) != (n_mels, T_keep):
+            raise ValueError(f"transfer_recording: keep must be a mask [n_mels, T_total] = [{n_mels}, {T_keep}], got "
+                             f"{tuple(keep.shape)}")
+        if not bool(torch.isfinite(keep).all()) or float(keep.min()) < 0 or float(keep.max()) > 1:
+            raise ValueError("transfer_recording: keep must be finite and lie in [0, 1]")
     guided = base_style is not None or float(guidance_scale) != 1.0
     if guided:
         if not math.isfinite(float(guidance_scale)):
@@ -112,13 +129,17 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     noise = torch.randn((N, latent, n_mels // 8, frames // 8), generator=torch.Generator().manual_seed(int(seed)))
     noise = noise.to(content.device)
 
+    keep_w = None if keep is None else longform.mask_windows(keep, frames, overlap).to(content.device)
+
     def guide_kw(b0, b1):
-        """content_style_transfer's guidance arguments for windows [b0, b1): none when unguided."""
+        """content_style_transfer's guidance and keep arguments for windows [b0, b1): none when neither is asked for."""
+        kw = {} if keep_w is None else {"keep": keep_w[b0:b1], "composite": bool(composite)}
         if not guided:
-            return {}
+            return kw
         if isinstance(base_style, str):
-            return {"guidance_scale": float(guidance_scale), "base_style": x[b0:b1]}
-        return {"guidance_scale": float(guidance_scale), "base_style": xb[torch.arange(b0, b1, device=xb.device) % Nb]}
+            return dict(kw, guidance_scale=float(guidance_scale), base_style=x[b0:b1])
+        return dict(kw, guidance_scale=float(guidance_scale),
+                    base_style=xb[torch.arange(b0, b1, device=xb.device) % Nb])
 
     if guided and not isinstance(base_style, str):
         Pb = audio.melspectrogram(base_style, sr=sr, n_mels=n_mels)
@@ -193,6 +214,17 @@ def load_model(checkpoint=None, device="cuda"):
     return model.to(device).eval()
 
 
+def _span(text):
+    """argparse type of --keep-time / --keep-band: "A:B" with A <= B as a pair of floats."""
+    try:
+        a, b = (float(v) for v in text.split(":"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected LOW:HIGH, got {text!r}") from None
+    if not (math.isfinite(a) and math.isfinite(b) and a <= b):
+        raise argparse.ArgumentTypeError(f"expected finite LOW <= HIGH, got {text!r}")
+    return (a, b)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="python -m models.transfer", description=__doc__.split("\n\n")[0])
     p.add_argument("--content", required=True, help="the recording to transfer (.wav, PCM16 or float32, any rate)")
@@ -221,6 +253,15 @@ def parse_args(argv=None):
     p.add_argument("--base-style", default=None, dest="base_style", metavar="{content|PATH}",
                    help="what the guidance steers away from: \"content\" (each window's own content, the default "
                         "when --guidance-scale is not 1) or a .wav")
+    p.add_argument("--keep-time", action="append", default=[], dest="keep_time", metavar="T0:T1", type=_span,
+                   help="leave the seconds T0 to T1 of the content as they are (needs --solver; repeatable)")
+    p.add_argument("--keep-band", action="append", default=[], dest="keep_band", metavar="F0:F1", type=_span,
+                   help="leave the mel bins whose centre frequency lies in F0 to F1 Hz as they are (needs --solver; "
+                        "repeatable)")
+    p.add_argument("--keep-feather", type=int, default=0, dest="keep_feather", metavar="N",
+                   help="ramp every kept region linearly over its N outermost frames (bins)")
+    p.add_argument("--no-composite", action="store_false", dest="composite",
+                   help="do not paste the content back over the kept region of the decoded windows")
     p.add_argument("--batch", type=int, default=8, help="windows per model call")
     p.add_argument("--seed", type=int, default=0)
     args = p.parse_args(argv)
@@ -232,6 +273,10 @@ def parse_args(argv=None):
         p.error("--guidance-scale must be finite")
     if (args.guidance_scale != 1.0 or args.base_style is not None) and args.solver is None:
         p.error("--guidance-scale / --base-style need --solver")
+    if (args.keep_time or args.keep_band) and args.solver is None:
+        p.error("--keep-time / --keep-band need --solver")
+    if args.keep_feather < 0:
+        p.error("--keep-feather must not be negative")
     if len(args.style) == 1:
         args.style = args.style[0]      # a single file: the string it always was
     return args
@@ -253,6 +298,10 @@ def main(argv=None):
         if base is not None and base != "content":
             base = ap.trim_silence(ap.load_audio_native(base)[0])
         guide = {"guidance_scale": args.guidance_scale, "base_style": base}
+    if args.keep_time or args.keep_band:
+        guide["keep"] = longform.keep_mask(1 + content.numel() // HOP, 128, sr, times=args.keep_time,
+                                           bands=args.keep_band, feather=args.keep_feather)
+        guide["composite"] = args.composite
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
                              num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
                              solver=args.solver, t_start=args.t_start, style_weights=args.style_weights,
