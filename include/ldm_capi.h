@@ -703,6 +703,11 @@ int ldm_batchnorm_backward_apply(const float* dy, const float* y, const float* x
 /* Backward of ldm_attention_core: dq [B,E,L], dkv [B,2E,S] (dK then dV). */
 int ldm_attention_backward(const float* q, const float* kv, const float* dout, float* dq, float* dkv, int32_t B,
                            int32_t E, int32_t heads, int32_t L, int32_t S, float scale, void* stream);
+/* 1 when ldm_attention_backward has a form for the shape (the MFMA form: L, S and the head dim multiples of 16
+ * within 160 KiB of LDS; the scalar form: (d*L + d*S + 2*L*S) floats within 64 KiB), 0 when it would fail with
+ * "head tile exceeds LDS budget" (e.g. d = 128 at L = S = 50); those shapes go to the pair
+ * ldm_attention_forward_lse / ldm_attention_backward_flash where the head dim allows. */
+int ldm_attention_backward_supported(int32_t E, int32_t heads, int32_t L, int32_t S);
 /* The same backward for any L, S (flash.hip), from the forward's out and lse (ldm_attention_forward_lse):
  * delta = rowsum(dO * O) into delta_ws [B,heads,L], then dK/dV (64 keys per block, q and dO streamed) and
  * dQ (64 queries per block, K and V streamed), deterministic. */

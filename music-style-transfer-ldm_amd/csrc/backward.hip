@@ -814,18 +814,37 @@ static int conv_backward_weight_impl(const ldm_conv_desc* d, const float* x, con
     return 0;
 }
 
+// The two forms of ldm_attention_backward and their LDS needs: the dispatch and ldm_attention_backward_supported
+// both go through these.
+static bool attn_bwd_mfma_shape(int d, int L, int S) { return L % 16 == 0 && S % 16 == 0 && d % 16 == 0; }
+static size_t attn_bwd_mfma_lds(int d, int L, int S) {
+    return ((size_t)d * (L + 1) + (size_t)d * (S + 1) + 2 * (size_t)L * (S + 1)) * sizeof(float);
+}
+static size_t attn_bwd_scalar_lds(int d, int L, int S) {
+    return ((size_t)d * L + (size_t)d * S + 2 * (size_t)L * S) * sizeof(float);
+}
+constexpr size_t kAttnBwdMfmaLds = 160 * 1024, kAttnBwdScalarLds = 64 * 1024;
+
+extern "C" int ldm_attention_backward_supported(int32_t E, int32_t heads, int32_t L, int32_t S) {
+    if (heads <= 0 || E <= 0 || E % heads != 0 || L <= 0 || S <= 0) return 0;
+    const int d = E / heads;
+    if (attn_bwd_mfma_shape(d, L, S) && attn_bwd_mfma_lds(d, L, S) <= kAttnBwdMfmaLds) return 1;
+    return attn_bwd_scalar_lds(d, L, S) <= kAttnBwdScalarLds ? 1 : 0;
+}
+
 extern "C" int ldm_attention_backward(const float* q, const float* kv, const float* dout, float* dq, float* dkv,
                                       int32_t B, int32_t E, int32_t heads, int32_t L, int32_t S, float scale,
                                       void* stream) {
-    LDM_REQUIRE(q && kv && dout && dq && dkv && B > 0 && heads > 0 && E % heads == 0, "attention_backward: bad argument");
+    LDM_REQUIRE(q && kv && dout && dq && dkv && B > 0 && heads > 0 && E > 0 && E % heads == 0 && L > 0 && S > 0,
+                "attention_backward: bad argument");
     const int d = E / heads;
-    if (L % 16 == 0 && S % 16 == 0 && d % 16 == 0) {
-        const size_t lds = ((size_t)d * (L + 1) + (size_t)d * (S + 1) + 2 * (size_t)L * (S + 1)) * sizeof(float);
-        if (lds <= 160 * 1024) {
+    if (attn_bwd_mfma_shape(d, L, S)) {
+        const size_t lds = attn_bwd_mfma_lds(d, L, S);
+        if (lds <= kAttnBwdMfmaLds) {
             static bool opted = false;
             if (!opted) {
                 LDM_HIP_TRY(hipFuncSetAttribute((const void*)attention_backward_mfma_kernel,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnBwdMfmaLds));
                 opted = true;
             }
             hipLaunchKernelGGL(attention_backward_mfma_kernel, dim3(B * heads), dim3(256), lds, (hipStream_t)stream, q,
@@ -834,8 +853,8 @@ extern "C" int ldm_attention_backward(const float* q, const float* kv, const flo
             return 0;
         }
     }
-    const size_t lds = ((size_t)d * L + (size_t)d * S + 2 * (size_t)L * S) * sizeof(float);
-    LDM_REQUIRE(lds <= 64 * 1024, "attention_backward: head tile exceeds LDS budget");
+    const size_t lds = attn_bwd_scalar_lds(d, L, S);
+    LDM_REQUIRE(lds <= kAttnBwdScalarLds, "attention_backward: head tile exceeds LDS budget");
     hipLaunchKernelGGL(attention_backward_kernel, dim3(B * heads), dim3(256), lds, (hipStream_t)stream, q, kv, dout, dq,
                        dkv, E, heads, L, S, scale);
     LDM_CHECK_LAUNCH("attention_backward_kernel");

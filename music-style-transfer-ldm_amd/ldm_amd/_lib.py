@@ -264,6 +264,7 @@ SIGNATURES = {
                                                c_int32, c_vp, ctypes.c_double, c_fp, c_vp]),
     "ldm_attention_backward": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          c_float, c_vp]),
+    "ldm_attention_backward_supported": (c_int32, [c_int32, c_int32, c_int32, c_int32]),
     "ldm_unscale_check": (c_int32, [c_vp, c_vp, c_vp, c_int32, c_int32, c_fp, c_vp, c_vp]),
     "ldm_adam_step": (c_int32, [c_vp, c_vp, c_vp, c_int32, c_int32, ctypes.c_double, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int32, c_int32, c_vp, c_vp]),

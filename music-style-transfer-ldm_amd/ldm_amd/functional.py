@@ -368,8 +368,9 @@ def _kl_backward(ctx, g):
 def attention_core(q, kv, heads):
     def fwd(store, q_, kv_):
         store["heads"] = heads
-        if store["grad"] and ops.attention_uses_flash(q_.shape[1], heads, q_.shape[2], kv_.shape[2]):
-            # wide maps: the KV-tiled kernels, whose backward needs the output and the per-query log-sum-exp
+        if store["grad"] and ops.attention_backward_uses_flash(q_.shape[1], heads, q_.shape[2], kv_.shape[2]):
+            # wide maps, and the maps within 64 tokens that the LDS-resident backward cannot hold: the KV-tiled
+            # kernels, whose backward needs the output and the per-query log-sum-exp
             out, lse = ops.attention_forward_lse(q_, kv_, heads)
             store["saved"] = (q_, kv_, out, lse)
             return out

@@ -889,6 +889,18 @@ def attention_uses_flash(E, heads, Lq, S):
     return max(Lq, S) > 64 and bool(L.load().ldm_attention_flash_supported(int(E), int(heads)))
 
 
+def attention_backward_uses_flash(E, heads, Lq, S):
+    """True when a differentiated attention takes the KV-tiled pair (attention_forward_lse /
+    attention_backward_flash): the forward is theirs anyway, or the LDS-resident backward has no form for the
+    shape (ldm_attention_backward_supported: d = 128 at 47-63 tokens that are no multiple of 16) and the head
+    dim is one the KV-tiled kernels carry."""
+    if attention_uses_flash(E, heads, Lq, S):
+        return True
+    lib = L.load()
+    return bool(lib.ldm_attention_flash_supported(int(E), int(heads))) and not bool(
+        lib.ldm_attention_backward_supported(int(E), int(heads), int(Lq), int(S)))
+
+
 def attention_forward_lse(q, kv, heads):
     """q [B,E,L], kv [B,2E,S] -> (out [B,E,L], lse [B,heads,L]) on the KV-tiled online-softmax kernel."""
     require_device(q, kv, dtype=None)
