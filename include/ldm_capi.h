@@ -225,7 +225,7 @@ int ldm_attention_folded_probs(const float* z, const float* kf, const float* bf,
  * [512,512,3,3]; kv the CA1 K/V projection [B,1024,16]); then per step y [B,2,8,512] (NHWC) = relu(sum over
  * (t, h, s) of u * p[b][h][l_t][s] + pos_bias[l][co]) with pos_bias [16][512] (position-major) and p from
  * ldm_attention_folded_probs.  dtype LDM_DT_F16 / _BF16 rounds the output to that type (operands stay fp32).
- * Used by ldm_ddim_sample when ldm_bneck_fold_supported(B, H, W): the canonical 16 x 64 latent, B <= 8
+ * Used by ldm_sample when ldm_bneck_fold_supported(B, H, W): the canonical 16 x 64 latent, B <= 8
  * (LDM_BNECK_FOLD=0 turns it off). */
 int32_t ldm_bneck_fold_supported(int32_t B, int32_t H, int32_t W);
 int ldm_bneck_fold_values(const float* w_fold, const float* kv, float* u, int32_t B, void* stream);
@@ -368,115 +368,80 @@ int ldm_unet_forward(const ldm_unet_shape* s, const ldm_unet_weights* w, const f
                      int32_t t_is_float, const float* s5, const float* s6, float* out, float* workspace,
                      void* stream);
 
-/* Reverse loop (style_conditioned_ddim_sample model.py:409-465 / content_style_ddim_sample :503-559):
- * x [B,C,H,W] updated in place over nsteps = len(times)-1 steps.  t_table [nsteps,B] int64 holds
- * times[i] repeated over the batch, coef_table [nsteps,4] the per-step coefficients.  x0_logs /
- * eps_logs (may be NULL) hold step i at x0_logs + i*log_step_stride ([B,C,H,W] each; stride 0 = dense
- * B*C*H*W), so a sub-batch can write straight into its slice of the full-batch logs.
- * workspace: ldm_ddim_workspace_floats(s, w, nsteps) floats, zero-filled before first use.
- * The time MLP for all steps is one launch before the loop; each step's update is fused into dec1's
- * epilogue.  Only launches: the caller may capture the whole loop into one hipGraph (the Python layer
- * does, with torch.cuda.CUDAGraph, splitting the batch into independent sub-batch chains on separate
- * streams so that one chain's launch / memory latency overlaps another's work). */
-int64_t ldm_ddim_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps);
-int ldm_ddim_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                    const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta,
-                    float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
-/* The same loop with the multistep solver's update (ldm_msolver_step) fused into dec1: coef_table [nsteps, 8]
- * (ForwardDiffusion.multistep_coefs), no eta.  Same time-MLP and K/V hoisting, fold and step-kernel selection,
- * workspace (ldm_ddim_workspace_floats) and log_step_stride meaning.  x0_logs is required: it is the solver's
- * history (step i reads the slot of step i-1; step 0 reads none).  eps_logs stays optional. */
-int ldm_msolver_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                       const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps,
-                       float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
-/* Style mixing: the same two loops attending over S5 / S6 style tokens per sample instead of the maps' own
- * H*W/16 / H*W/64: s5 [B,256,S5], s6 [B,512,S6] (R references stacked along the map's height: reference r owns
- * keys [r*L, (r+1)*L)), key_bias5 [B,S5] / key_bias6 [B,S6] as in ldm_attention_folded_keys (log of each
- * reference's weight; NULL = none).  The K/V projections and the key fold run over S tokens, the bias is folded
- * into bf once per loop, and each step's two attentions stream the keys.  Needs use_fold (an error otherwise);
- * with S6 != H*W/64 or a key_bias6 the bottleneck runs without its value fold.  Workspace:
- * ldm_ddim_workspace_floats_mix.  With S5 = H*W/16, S6 = H*W/64 and no bias these are ldm_ddim_sample /
- * ldm_msolver_sample / ldm_ddim_workspace_floats. */
-int64_t ldm_ddim_workspace_floats_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5,
-                                      int32_t S6);
-int ldm_ddim_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                        const float* s6, int32_t S5, int32_t S6, const float* key_bias5, const float* key_bias6,
-                        const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta, float* x0_logs,
-                        float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
-int ldm_msolver_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                           const float* s6, int32_t S5, int32_t S6, const float* key_bias5, const float* key_bias6,
-                           const int64_t* t_table, const float* coef_table, int32_t nsteps, float* x0_logs,
-                           float* eps_logs, int64_t log_step_stride, float* workspace, void* stream);
-/* Style guidance: the same two loops steered from a base style towards the target.  Every step evaluates the
- * denoiser under both conditions on the same x and t and steps on
- *   eps = e_b + scale[b] * (e_t - e_b)          (fp32, one rounding per operation: d = e_t - e_b; g = s d; e = e_b + g)
- * with e_t / e_b dec1's outputs (after its output rounding with 16-bit operands); eps feeds the unchanged DDIM /
- * multistep update, the logs ([n, B, C, H, W]) record the guided x0 / eps, and the multistep history is the guided
- * x0.  scale = 1 is the unguided sampler on the target up to one rounding, scale = 0 the one on the base.
- * s->B is the caller's batch B; x is [B, C, H, W] in and out; s5 / s6 (target) and s5_base / s6_base are separate
- * [B, ...] maps with the same key counts S5 / S6 (0 = the maps' own, else as in the *_mix entries, which needs
- * use_fold), each with its optional key biases; guide_scale is a device array [B] of finite fp32.  The body runs the
- * UNet at batch 2B (targets, then bases): w holds the plans and weights bound for the shape with batch 2B
- * (ldm_unet_make_plans on it).  One exception is allowed with use_step: the plans may be those of a larger batch (a
- * sub-batch chain running the whole batch's plans, so that a sample's arithmetic does not depend on how a batch is
- * split), provided the two K/V projection plans need no split-K workspace (ws_floats == 0): a plan's kind, tile and
- * weight pack do not depend on the batch, the grids come from s, and those two projections are the step-kernel
- * path's only planned launches.  Without use_step dec1's bound plan must be of kind 0, 1 or 2 (what
- * ldm_unet_make_plans produces); another kind is an error.
- * The workspace is ldm_ddim_workspace_floats_guided's, more than twice the unguided one.  The entries take no size, so
- * before anything is launched they ask the runtime for the extent of the device allocation that holds `workspace`
- * and report an error if it ends before the guided size (a buffer sized by ldm_ddim_workspace_floats).  That is exact
- * for a buffer that is an allocation of its own; one carved out of a larger pool is only known to end inside the
- * pool, and the check is skipped under stream capture (run the loop eagerly once before capturing it).
- * dec1 runs as two launches at batch B: the base half as a plain conv, the target half with the guidance and the
- * update fused, storing the new state for both halves.
- * ldm_guide_eps: the same arithmetic on whole tensors, out[i] = e_b[i] + scale[i / per_sample] * (e_t[i] - e_b[i])
- * for B * per_sample elements (out may alias e_t or e_b). */
-int64_t ldm_ddim_workspace_floats_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5,
-                                         int32_t S6);
-int ldm_ddim_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                           const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
-                           const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
-                           const float* key_bias6_base, const float* guide_scale, const int64_t* t_table,
-                           const float* coef_table, int32_t nsteps, float eta, float* x0_logs, float* eps_logs,
-                           int64_t log_step_stride, float* workspace, void* stream);
-int ldm_msolver_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                              const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
-                              const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
-                              const float* key_bias6_base, const float* guide_scale, const int64_t* t_table,
-                              const float* coef_table, int32_t nsteps, float* x0_logs, float* eps_logs,
-                              int64_t log_step_stride, float* workspace, void* stream);
+/* ---- the reverse loop: one entry, its options in one struct ------------------------------------------------
+ * Replaces style_conditioned_ddim_sample (model.py:409-465) / content_style_ddim_sample (:503-559).  x is updated in
+ * place over nsteps = len(times)-1 steps.  The time MLP for all steps is one launch before the loop, the style
+ * maps' K/V projections likewise, and each step's update is fused into dec1's epilogue.  Only launches: the caller
+ * may capture the whole loop into one hipGraph (the Python layer does, with torch.cuda.CUDAGraph, splitting the
+ * batch into independent sub-batch chains on separate streams so that one chain's launch / memory latency overlaps
+ * another's work).  Every option is off when its fields are NULL / 0, and the options compose. */
+#define LDM_SOLVER_DDIM 0        /* coef_table [nsteps,4] (ldm_ddim_step's rows), eta used, x0_logs optional */
+#define LDM_SOLVER_MULTISTEP 1   /* coef_table [nsteps,8] (ldm_msolver_step's rows, ForwardDiffusion.multistep_coefs), */
+                                 /* eta ignored, x0_logs required: the history (step i reads step i-1's slot)         */
+
+typedef struct ldm_sample_args {
+    int32_t solver, nsteps;   /* LDM_SOLVER_*; nsteps 0 returns at once */
+    float eta;
+    /* Style mixing: the loop attends over S5 / S6 style tokens per sample instead of the maps' own H*W/16 / H*W/64
+     * (0 = the maps' own): s5 [B,256,S5], s6 [B,512,S6] (R references stacked along the map's height: reference r
+     * owns keys [r*L, (r+1)*L)), key_bias5 [B,S5] / key_bias6 [B,S6] as in ldm_attention_folded_keys (log of each
+     * reference's weight; NULL = none).  The K/V projections and the key fold run over S tokens, the bias is folded
+     * into bf once per loop, and each step's two attentions stream the keys.  Other key counts or a bias need
+     * use_fold (an error otherwise); with S6 != H*W/64 or a key_bias6 the bottleneck runs without its value fold. */
+    int32_t S5, S6;
+    float* x;                 /* [B,C,H,W], in place */
+    const float *s5, *s6, *key_bias5, *key_bias6;
+    /* Style guidance (all five NULL = none; s5_base, s6_base and guide_scale go together, the biases are optional):
+     * every step evaluates the denoiser under the target maps (s5 / s6) and the base maps on the same x and t and
+     * steps on
+     *   eps = e_b + scale[b] * (e_t - e_b)      (fp32, one rounding per operation: d = e_t - e_b; g = s d; e = e_b + g)
+     * with e_t / e_b dec1's outputs (after its output rounding with 16-bit operands); eps feeds the unchanged update,
+     * the logs record the guided x0 / eps, and the multistep history is the guided x0.  scale = 1 is the unguided
+     * sampler on the target up to one rounding, scale = 0 the one on the base.  The base maps and biases are
+     * separate [B, ...] arrays with the target's key counts; guide_scale is a device array [B] of finite fp32.
+     * s->B stays the caller's batch B, but the body runs the UNet at batch 2B (targets, then bases): w holds the
+     * plans and weights bound for the shape with batch 2B (ldm_unet_make_plans on it).  One exception is allowed
+     * with use_step: the plans may be those of a larger batch (a sub-batch chain running the whole batch's plans, so
+     * that a sample's arithmetic does not depend on how a batch is split), provided the two K/V projection plans need
+     * no split-K workspace (ws_floats == 0): a plan's kind, tile and weight pack do not depend on the batch, the grids
+     * come from s, and those two projections are the step-kernel path's only planned launches.  Without use_step
+     * dec1's bound plan must be of kind 0, 1 or 2 (what ldm_unet_make_plans produces); another kind is an error.
+     * dec1 runs as two launches at batch B: the base half as a plain conv, the target half with the guidance and the
+     * update fused, storing the new state for both halves. */
+    const float *s5_base, *s6_base, *key_bias5_base, *key_bias6_base, *guide_scale;
+    /* Regional keep (all four NULL = none; one NULL beside the others is an error): after every step's update the
+     * state is blended with the content's own noising trajectory under a keep weight, per element in fp32, one
+     * rounding per operation (keep_blend, csrc/common.h):
+     *     known = a_i * z0 + b_i * n0;   x_next = (1 - w) * x_update + w * known
+     * z0 / n0 [B,C,H,W]: the clean latent and the q_sample noise; keep [B,H,W] in [0,1] (1 = keep the content,
+     * shared by the channels); keep_coef [nsteps,2] = {a_i, b_i} (device; ForwardDiffusion.keep_coefs).  The x0 /
+     * eps logs and the 2M history stay the model's own prediction. */
+    const float *z0, *n0, *keep, *keep_coef;
+    const int64_t* t_table;   /* [nsteps,B]: times[i] repeated over the batch */
+    const float* coef_table;  /* per-step coefficient rows of the solver */
+    /* step i at x0_logs + i*log_step_stride ([B,C,H,W] each; stride 0 = dense B*C*H*W), so a sub-batch can write
+     * straight into its slice of the full-batch logs; either may be NULL (x0_logs not for the multistep solver) */
+    float *x0_logs, *eps_logs;
+    int64_t log_step_stride;
+    float* workspace;         /* ldm_sample_workspace_floats(s, w, this struct) floats, zero-filled before first use */
+    void* stream;
+} ldm_sample_args;
+
+/* The workspace size of ldm_sample(s, w, a): size with the struct that will be passed.  Reads only nsteps, S5, S6
+ * and whether the guidance / the keep are on (any pointer of the group set).  Negative for a NULL s or a, a
+ * negative nsteps / S5 / S6 or a batch <= 0.  A guided workspace is more than twice the unguided one. */
+int64_t ldm_sample_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a);
+/* The struct carries no buffer size, so before anything is launched ldm_sample asks the runtime for the extent of the
+ * device allocation that holds `workspace` and reports an error if it ends before ldm_sample_workspace_floats(s, w, a)
+ * (a buffer sized for another configuration).  That is exact for a buffer that is an allocation of its own; one
+ * carved out of a larger pool is only known to end inside the pool, and the check is skipped under stream capture
+ * (run the loop eagerly once before capturing it). */
+int ldm_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a);
+/* The guidance and the keep arithmetic on whole tensors.  ldm_guide_eps: out[i] = e_b[i] + scale[i / per_sample] *
+ * (e_t[i] - e_b[i]) for B * per_sample elements (out may alias e_t or e_b).  ldm_keep_blend: in place on x (NCHW),
+ * with one row coef = {a, b}. */
 int ldm_guide_eps(const float* e_t, const float* e_b, const float* scale, int64_t per_sample, int32_t B, float* out,
                   void* stream);
-
-/* ---- regional transfer: hold masked content fixed (unet.hip sample_loop's Keep) ----------
- * After every step's update the sampler state is blended with the content's own noising trajectory under a keep
- * weight, per element in fp32, one rounding per operation (keep_blend, csrc/common.h):
- *     known = a_i * z0 + b_i * n0;   x_next = (1 - w) * x_update + w * known
- * z0 / n0 [B,C,H,W]: the clean latent and the q_sample noise; keep [B,H,W] in [0,1] (1 = keep the content, shared by
- * the channels); keep_coef [nsteps,2] (device; ForwardDiffusion.keep_coefs).  The x0 / eps logs and the 2M history
- * stay the model's own prediction.  The entries take the guided entries' argument list: a NULL base and a NULL scale
- * mean unguided, S5 = S6 = 0 the maps' own key counts, key_bias* are optional.  With keep == NULL (then z0, n0 and
- * keep_coef NULL as well) they are the existing entries argument for argument.  One of the four keep operands NULL
- * beside the others, or a workspace whose allocation ends before ldm_ddim_workspace_floats_keep(.., guided)
- * (checked like the guided entries' workspace), is an error reported before anything is launched.
- * ldm_keep_blend: the same arithmetic on whole NCHW tensors, in place on x, with one row coef = {a, b}. */
-int64_t ldm_ddim_workspace_floats_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5,
-                                       int32_t S6, int32_t guided);
-int ldm_ddim_sample_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
-                         const float* s5_base, const float* s6_base, int32_t S5, int32_t S6, const float* key_bias5,
-                         const float* key_bias6, const float* key_bias5_base, const float* key_bias6_base,
-                         const float* guide_scale, const float* z0, const float* n0, const float* keep,
-                         const float* keep_coef, const int64_t* t_table, const float* coef_table, int32_t nsteps,
-                         float eta, float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
-                         void* stream);
-int ldm_msolver_sample_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                            const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
-                            const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
-                            const float* key_bias6_base, const float* guide_scale, const float* z0, const float* n0,
-                            const float* keep, const float* keep_coef, const int64_t* t_table, const float* coef_table,
-                            int32_t nsteps, float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
-                            void* stream);
 int ldm_keep_blend(float* x, const float* z0, const float* n0, const float* keep, const float* coef, int32_t B, int32_t C,
                    int64_t HW, void* stream);
 
@@ -576,7 +541,7 @@ int ldm_mel_stitch(const float* y, const float* ref_db, int32_t N, int32_t n_mel
  * (conv [Cout][Cin][3][3], transposed conv [Cin][Cout][3][3]).  ldm_step_conv runs one layer on NHWC
  * activations (latent [B,H,W] with H, W multiples of 8): y = act(conv(x) + bias) (+ bcast[b][c] for
  * enc2) (+ skip for dec4..dec2); bias is [Cout], or [Hout*Wout][Cout] for the folded enc4 / bottleneck.
- * dec1 only runs fused with the DDIM update inside ldm_ddim_sample. */
+ * dec1 only runs fused with the sampler's update inside ldm_sample. */
 int64_t ldm_step_packed_floats(int32_t layer);
 int ldm_step_pack_weight(int32_t layer, const float* w, float* packed, void* stream);
 /* The pack for an operand precision: LDM_DT_F32 as ldm_step_pack_weight; LDM_DT_F16 / LDM_DT_BF16 write the

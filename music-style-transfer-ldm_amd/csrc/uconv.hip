@@ -1,5 +1,5 @@
 // Step kernels of the reverse loop: the nine convolutions of UNet.forward (model.py:178-194, :205-229)
-// as fixed-structure implicit GEMMs for gfx950, used by ldm_ddim_sample when use_step != 0.
+// as fixed-structure implicit GEMMs for gfx950, used by ldm_sample when use_step != 0.
 //
 // Why a second conv family next to conv.hip: at the sampling batch (B = 8 on a 16x64 latent) every layer
 // is a 0.3-0.6 GFLOP GEMM whose output is only 64K-512K values, so a launch is ~256 blocks that each own
@@ -1496,7 +1496,7 @@ extern "C" int ldm_step_conv_ws(int32_t layer, int32_t B, int32_t H, int32_t W, 
     s.skip = skip;
     s.y = y;
     s.ws = workspace;
-    LDM_REQUIRE(layer != 8, "ldm_step_conv: dec1 runs fused with the DDIM update (ldm_ddim_sample)");
+    LDM_REQUIRE(layer != 8, "ldm_step_conv: dec1 runs fused with the DDIM update (ldm_sample)");
     return step_conv(layer, B, H, W, s, (hipStream_t)stream);
 }
 
@@ -1547,7 +1547,7 @@ extern "C" int ldm_step_conv_dt(int32_t layer, int32_t B, int32_t H, int32_t W, 
     s.bcast = bcast;
     s.skip = skip;
     s.y = y;
-    LDM_REQUIRE(layer != 8, "ldm_step_conv: dec1 runs fused with the DDIM update (ldm_ddim_sample)");
+    LDM_REQUIRE(layer != 8, "ldm_step_conv: dec1 runs fused with the DDIM update (ldm_sample)");
     return step_conv(layer, B, H, W, s, (hipStream_t)stream);
 }
 #endif   // UCONV_TEMPLATES_ONLY

@@ -128,7 +128,7 @@ static bool use_bneck_fold(const ldm_unet_shape& s, const ldm_unet_weights* w) {
 }
 
 // S5 / S6: key counts of CA2 / CA1 (style mixing: several references stacked along the keys); 0 = the map's own
-// token count, which is every caller but the *_mix loops.  Only the K/V projections and the folded keys scale.
+// token count, which is every caller but a style mix.  Only the K/V projections and the folded keys scale.
 static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float* base, int64_t S5 = 0, int64_t S6 = 0,
                     bool guided = false) {
     const int64_t B = s.B, nf = s.nf, HW = (int64_t)s.H * s.W;
@@ -204,9 +204,15 @@ struct DdimFuse {
     int64_t kstride;   // floats between the region's parts
 };
 
-static void keep_epi(EpiArgs& ep, const DdimFuse* fuse) {
-    if (!fuse || !fuse->kw) return;
-    ep.keep_z0 = fuse->kz0, ep.keep_n0 = fuse->kn0, ep.keep_w = fuse->kw, ep.keep_coef = fuse->kcoef;
+// dec1's epilogue with the update fused in: the solver's row, the state, the logs and the keep
+static void fuse_epi(EpiArgs& ep, const DdimFuse& fuse) {
+    if (fuse.msolver) ep.ms_coef = fuse.coef, ep.ms_x0_prev = fuse.x0_prev;
+    else ep.ddim_coef = fuse.coef;
+    ep.ddim_eta = fuse.eta;
+    ep.ddim_x = fuse.x;
+    ep.ddim_x0_log = fuse.x0_log;
+    ep.ddim_eps_log = fuse.eps_log;
+    if (fuse.kw) ep.keep_z0 = fuse.kz0, ep.keep_n0 = fuse.kn0, ep.keep_w = fuse.kw, ep.keep_coef = fuse.kcoef;
 }
 
 static int conv_call(const ldm_unet_shape& s, float* convws, int layer, const ldm_conv_plan& plan, const float* x, const float* w,
@@ -221,15 +227,7 @@ static int conv_call(const ldm_unet_shape& s, float* convws, int layer, const ld
     ep.act = act;
     ep.bcast = bcast;
     ep.skip = skip;
-    if (fuse) {
-        if (fuse->msolver) ep.ms_coef = fuse->coef, ep.ms_x0_prev = fuse->x0_prev;
-        else ep.ddim_coef = fuse->coef;
-        ep.ddim_eta = fuse->eta;
-        ep.ddim_x = fuse->x;
-        ep.ddim_x0_log = fuse->x0_log;
-        ep.ddim_eps_log = fuse->eps_log;
-        keep_epi(ep, fuse);
-    }
+    if (fuse) fuse_epi(ep, *fuse);
     return conv_forward_ex(d, plan, x, w, ep, y, convws, st);
 }
 
@@ -262,16 +260,10 @@ static int dec1_call(const ldm_unet_shape& s, const ldm_unet_weights& w, const f
     eb.act = LDM_ACT_NONE;
     LDM_TRY(conv_forward_ex(d, plan, d2 + fuse->gB * HW * s.nf, w.conv_w[8], eb, fuse->eb, convws, st));
     EpiArgs ep = eb;
-    if (fuse->msolver) ep.ms_coef = fuse->coef, ep.ms_x0_prev = fuse->x0_prev;
-    else ep.ddim_coef = fuse->coef;
-    ep.ddim_eta = fuse->eta;
-    ep.ddim_x = fuse->x;
-    ep.ddim_x0_log = fuse->x0_log;
-    ep.ddim_eps_log = fuse->eps_log;
+    fuse_epi(ep, *fuse);
     ep.guide_eb = fuse->eb;
     ep.guide_scale = fuse->gscale;
     ep.ddim_x2 = fuse->x + fuse->gB * HW * s.C;
-    keep_epi(ep, fuse);
     return conv_forward_ex(d, plan, d2, w.conv_w[8], ep, nullptr, convws, st);
 }
 
@@ -480,18 +472,18 @@ extern "C" int ldm_unet_forward(const ldm_unet_shape* s, const ldm_unet_weights*
 
 // The reverse loop of both samplers.  msolver: coef_table is [nsteps, 8] (multistep rows) and every step i > 0 reads
 // step i-1's slot of x0_logs as its history (a first-order row there carries c_1 = 0); step 0 has none to read.
-// Style mixing (S5 / S6 > 0 and key_bias5 / key_bias6, the *_mix entries): s5 / s6 hold S5 / S6 style tokens per
+// Style mixing (S5 / S6 > 0 and key_bias5 / key_bias6): s5 / s6 hold S5 / S6 style tokens per
 // sample, the K/V projections and the key fold run over them, the bias goes into the folded keys' bias, and the
 // two attention launches of each step stream the keys (stylemix.hip).  With the maps' own counts and no bias every
 // call below is the one it always was.
-// Style guidance (the *_guided entries, g != NULL): every step evaluates the denoiser under the target and under a
+// Style guidance (g != NULL): every step evaluates the denoiser under the target and under a
 // base style and steps on eps = e_b + scale (e_t - e_b) (guide_eps).  The body runs at twice the caller's batch,
 // samples [0, B) under the target maps and [B, 2B) under the base maps, on a doubled sampler state whose halves
 // stay bitwise equal; w holds the doubled batch's plans.  Only dec1 differs (dec1_call / unet_step_kernels).
 struct Guide {
     const float *s5_base, *s6_base, *key_bias5_base, *key_bias6_base, *scale;
 };
-// The regional keep (the *_keep entries, k != NULL): after every step's update the state is blended with the content's
+// The regional keep (k != NULL): after every step's update the state is blended with the content's
 // own noising trajectory coef[i][0] z0 + coef[i][1] n0 under the keep weights w [B, H, W] (keep_blend); the logs and
 // the 2M history stay the model's prediction.  Only dec1's epilogue differs.  The step kernels read z0 / n0 in the
 // state's NHWC layout from a keep region behind the time embeddings (keep_region_floats), filled once per loop.
@@ -546,7 +538,7 @@ static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, floa
     LDM_REQUIRE(!mix || w->use_fold, "style mix: the reverse loop attends over several references only with the "
                                      "folded cross-attentions (use_fold)");
     UNetWs ws = carve(*s, w, workspace, S5, S6, g != nullptr);
-    float* temb_all = workspace + ws.total;   // [nsteps*B, 128] (ldm_ddim_workspace_floats[_guided])
+    float* temb_all = workspace + ws.total;   // [nsteps*B, 128] (ldm_sample_workspace_floats)
     const int64_t dense = (int64_t)sc->B * s->C * s->H * s->W;   // one step of the logs: the caller's batch
     LDM_REQUIRE(log_step_stride == 0 || log_step_stride >= dense, "ddim_sample: log stride smaller than a step");
     const int64_t n = log_step_stride ? log_step_stride : dense;
@@ -653,84 +645,28 @@ static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, floa
     return 0;
 }
 
-extern "C" int ldm_ddim_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                               const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps,
-                               float eta, float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
-                               void* stream) {
-    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace, "ddim_sample: null argument");
-    LDM_REQUIRE(nsteps >= 0, "ddim_sample: negative step count");
-    if (nsteps == 0) return 0;
-    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, eta, x0_logs, eps_logs, log_step_stride, workspace,
-                       stream, false);
+// ---- the one sampler entry (ldm_capi.h ldm_sample_args) ----------------------------------------------------------
+// An option is on when any of its pointers is set; ldm_sample then requires the rest of that group.
+static bool guidance_on(const ldm_sample_args& a) { return a.s5_base || a.s6_base || a.guide_scale; }
+static bool keep_on(const ldm_sample_args& a) { return a.z0 || a.n0 || a.keep || a.keep_coef; }
+
+// The unguided carve at the caller's batch, or the guided one at twice it; then the time embeddings of every step
+// (guided: the doubled rows behind the caller's) and, with the keep, its region.
+extern "C" int64_t ldm_sample_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a) {
+    if (!s || !a || a->nsteps < 0 || a->S5 < 0 || a->S6 < 0 || s->B <= 0) return -1;
+    const bool guided = guidance_on(*a);
+    ldm_unet_shape sh = *s;
+    if (guided) sh.B = 2 * s->B;
+    const int64_t n = carve(sh, w, nullptr, a->S5, a->S6, guided).total + (int64_t)a->nsteps * (guided ? 3 : 1) * s->B * 128;
+    return keep_on(*a) ? n + keep_region_floats(*s, a->nsteps, guided) : n;
 }
 
-// The multistep (DPM-Solver++(2M) / first-order) twin: same hoisting, fold and step selection, workspace
-// (ldm_ddim_workspace_floats) and log_step_stride meaning; x0_logs is the solver's history and required.
-extern "C" int ldm_msolver_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                                  const float* s6, const int64_t* t_table, const float* coef_table, int32_t nsteps,
-                                  float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace,
-                                  void* stream) {
-    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace && x0_logs, "msolver_sample: null argument");
-    LDM_REQUIRE(nsteps >= 0, "msolver_sample: negative step count");
-    if (nsteps == 0) return 0;
-    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs, log_step_stride, workspace,
-                       stream, true);
-}
-
-extern "C" int64_t ldm_ddim_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps) {
-    if (!s || nsteps < 0) return -1;
-    return carve(*s, w, nullptr).total + (int64_t)nsteps * s->B * 128;
-}
-
-// ---- style mixing: the same loops over S5 / S6 style tokens per sample with an optional key bias ----------------
-static int mix_args_ok(const ldm_unet_shape* s, int32_t S5, int32_t S6) {
-    LDM_REQUIRE(s && S5 > 0 && S6 > 0, "style mix: key counts must be positive");
-    return 0;
-}
-
-extern "C" int64_t ldm_ddim_workspace_floats_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps,
-                                                 int32_t S5, int32_t S6) {
-    if (!s || nsteps < 0 || S5 <= 0 || S6 <= 0) return -1;
-    return carve(*s, w, nullptr, S5, S6).total + (int64_t)nsteps * s->B * 128;
-}
-
-extern "C" int ldm_ddim_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                                   const float* s6, int32_t S5, int32_t S6, const float* key_bias5,
-                                   const float* key_bias6, const int64_t* t_table, const float* coef_table,
-                                   int32_t nsteps, float eta, float* x0_logs, float* eps_logs, int64_t log_step_stride,
-                                   float* workspace, void* stream) {
-    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace, "ddim_sample_mix: null argument");
-    LDM_REQUIRE(nsteps >= 0, "ddim_sample_mix: negative step count");
-    LDM_TRY(mix_args_ok(s, S5, S6));
-    if (nsteps == 0) return 0;
-    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, eta, x0_logs, eps_logs, log_step_stride, workspace,
-                       stream, false, S5, S6, key_bias5, key_bias6);
-}
-
-extern "C" int ldm_msolver_sample_mix(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                                      const float* s6, int32_t S5, int32_t S6, const float* key_bias5,
-                                      const float* key_bias6, const int64_t* t_table, const float* coef_table,
-                                      int32_t nsteps, float* x0_logs, float* eps_logs, int64_t log_step_stride,
-                                      float* workspace, void* stream) {
-    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace && x0_logs, "msolver_sample_mix: null argument");
-    LDM_REQUIRE(nsteps >= 0, "msolver_sample_mix: negative step count");
-    LDM_TRY(mix_args_ok(s, S5, S6));
-    if (nsteps == 0) return 0;
-    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs, log_step_stride, workspace,
-                       stream, true, S5, S6, key_bias5, key_bias6);
-}
-
-// ---- style guidance: the same loops under a target and a base style (sample_loop's Guide) -----------------------
-extern "C" int64_t ldm_ddim_workspace_floats_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps,
-                                                    int32_t S5, int32_t S6);
-
-// The entries take no buffer size, and the guided workspace is more than twice the unguided one: a buffer sized by
-// ldm_ddim_workspace_floats would be written past its end.  Before anything is launched the extent of the device
-// allocation that holds `workspace` is asked of the runtime and compared with the guided size.  This is exact for a
+// The struct carries no buffer size, and the sizes differ by more than a factor of two between configurations: a
+// buffer sized for another one would be written past its end.  Before anything is launched the extent of the device
+// allocation that holds `workspace` is asked of the runtime and compared with `need` floats.  This is exact for a
 // buffer that is an allocation of its own; a buffer carved from a larger pool is only known to end inside the pool.
 // Skipped under stream capture (a captured loop is run eagerly first) and where the runtime does not know the pointer.
-// need: the size in floats the entry's own function gives (ldm_ddim_workspace_floats_guided / _keep), named by `fn`.
-static int workspace_extent_ok(int64_t need, const char* fn, const float* workspace, void* stream) {
+static int workspace_extent_ok(int64_t need, const float* workspace, void* stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
         (void)hipGetLastError();
@@ -743,131 +679,36 @@ static int workspace_extent_ok(int64_t need, const char* fn, const float* worksp
         (void)hipGetLastError();
         return 0;
     }
-    LDM_REQUIRE(need > 0, "guided / keep sample: bad shape for the workspace size");
+    LDM_REQUIRE(need > 0, "sample: bad shape for the workspace size");
     const int64_t avail = (int64_t)(((const char*)base + size) - (const char*)workspace);
-    LDM_REQUIRE(avail >= need * 4, std::string("guided / keep sample: the workspace's allocation ends before the size ") + fn +
-                                       " gives (was it sized by another workspace function?)");
-    return 0;
-}
-static int guided_workspace_ok(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps, int32_t S5, int32_t S6,
-                               const float* workspace, void* stream) {
-    return workspace_extent_ok(ldm_ddim_workspace_floats_guided(s, w, nsteps, S5, S6), "ldm_ddim_workspace_floats_guided",
-                               workspace, stream);
-}
-
-static int guided_args_ok(const ldm_unet_shape* s, const float* s5_base, const float* s6_base, const float* guide_scale,
-                          int32_t S5, int32_t S6) {
-    LDM_REQUIRE(s5_base && s6_base, "guided sample: null base style maps");
-    LDM_REQUIRE(guide_scale, "guided sample: null guidance scale");
-    LDM_REQUIRE(S5 >= 0 && S6 >= 0, "guided sample: negative key count");
-    LDM_REQUIRE(s->B > 0 && s->B <= (1 << 20), "guided sample: bad batch");
+    LDM_REQUIRE(avail >= need * 4, "sample: the workspace's allocation ends before the size ldm_sample_workspace_floats "
+                                   "gives for these arguments (was it sized for another configuration?)");
     return 0;
 }
 
-extern "C" int64_t ldm_ddim_workspace_floats_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps,
-                                                    int32_t S5, int32_t S6) {
-    if (!s || nsteps < 0 || S5 < 0 || S6 < 0 || s->B <= 0) return -1;
-    ldm_unet_shape sh = *s;
-    sh.B = 2 * s->B;
-    return carve(sh, w, nullptr, S5, S6, true).total + (int64_t)nsteps * 3 * s->B * 128;
-}
-
-extern "C" int ldm_ddim_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                                      const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
-                                      const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
-                                      const float* key_bias6_base, const float* guide_scale, const int64_t* t_table,
-                                      const float* coef_table, int32_t nsteps, float eta, float* x0_logs, float* eps_logs,
-                                      int64_t log_step_stride, float* workspace, void* stream) {
-    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace, "ddim_sample_guided: null argument");
-    LDM_REQUIRE(nsteps >= 0, "ddim_sample_guided: negative step count");
-    LDM_TRY(guided_args_ok(s, s5_base, s6_base, guide_scale, S5, S6));
-    if (nsteps == 0) return 0;
-    LDM_TRY(guided_workspace_ok(s, w, nsteps, S5, S6, workspace, stream));
-    const Guide g{s5_base, s6_base, key_bias5_base, key_bias6_base, guide_scale};
-    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, eta, x0_logs, eps_logs, log_step_stride, workspace,
-                       stream, false, S5, S6, key_bias5, key_bias6, &g);
-}
-
-extern "C" int ldm_msolver_sample_guided(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                                         const float* s6, const float* s5_base, const float* s6_base, int32_t S5,
-                                         int32_t S6, const float* key_bias5, const float* key_bias6,
-                                         const float* key_bias5_base, const float* key_bias6_base,
-                                         const float* guide_scale, const int64_t* t_table, const float* coef_table,
-                                         int32_t nsteps, float* x0_logs, float* eps_logs, int64_t log_step_stride,
-                                         float* workspace, void* stream) {
-    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace && x0_logs,
-                "msolver_sample_guided: null argument");
-    LDM_REQUIRE(nsteps >= 0, "msolver_sample_guided: negative step count");
-    LDM_TRY(guided_args_ok(s, s5_base, s6_base, guide_scale, S5, S6));
-    if (nsteps == 0) return 0;
-    LDM_TRY(guided_workspace_ok(s, w, nsteps, S5, S6, workspace, stream));
-    const Guide g{s5_base, s6_base, key_bias5_base, key_bias6_base, guide_scale};
-    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs, log_step_stride, workspace,
-                       stream, true, S5, S6, key_bias5, key_bias6, &g);
-}
-
-// ---- regional keep: the same loops with the state held on the content's trajectory under a mask (sample_loop's Keep)
-extern "C" int64_t ldm_ddim_workspace_floats_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, int32_t nsteps,
-                                                  int32_t S5, int32_t S6, int32_t guided) {
-    if (!s || nsteps < 0 || S5 < 0 || S6 < 0 || s->B <= 0) return -1;
-    int64_t base;
+extern "C" int ldm_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a) {
+    LDM_REQUIRE(s && w && a, "sample: null argument");
+    LDM_REQUIRE(a->solver == LDM_SOLVER_DDIM || a->solver == LDM_SOLVER_MULTISTEP, "sample: unknown solver");
+    const bool msolver = a->solver == LDM_SOLVER_MULTISTEP;
+    LDM_REQUIRE(a->x && a->s5 && a->s6 && a->t_table && a->coef_table && a->workspace && (!msolver || a->x0_logs),
+                "sample: null argument");
+    LDM_REQUIRE(a->nsteps >= 0, "sample: negative step count");
+    LDM_REQUIRE(a->S5 >= 0 && a->S6 >= 0, "sample: negative key count");
+    const bool guided = guidance_on(*a), keep = keep_on(*a);
     if (guided) {
-        base = ldm_ddim_workspace_floats_guided(s, w, nsteps, S5, S6);
+        LDM_REQUIRE(a->s5_base && a->s6_base, "guided sample: null base style maps");
+        LDM_REQUIRE(a->guide_scale, "guided sample: null guidance scale");
+        LDM_REQUIRE(s->B > 0 && s->B <= (1 << 20), "guided sample: bad batch");
     } else {
-        const int L2 = s->H * s->W / 16, L1 = s->H * s->W / 64;
-        base = carve(*s, w, nullptr, S5 > 0 ? S5 : L2, S6 > 0 ? S6 : L1).total + (int64_t)nsteps * s->B * 128;
+        LDM_REQUIRE(!a->key_bias5_base && !a->key_bias6_base, "sample: base key biases without a base style");
     }
-    return base < 0 ? base : base + keep_region_floats(*s, nsteps, guided != 0);
-}
-
-static int keep_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
-                       const float* s5_base, const float* s6_base, int32_t S5, int32_t S6, const float* key_bias5,
-                       const float* key_bias6, const float* key_bias5_base, const float* key_bias6_base,
-                       const float* guide_scale, const float* z0, const float* n0, const float* keep,
-                       const float* keep_coef, const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta,
-                       float* x0_logs, float* eps_logs, int64_t log_step_stride, float* workspace, void* stream,
-                       bool msolver) {
-    LDM_REQUIRE(s && w && x && s5 && s6 && t_table && coef_table && workspace && (!msolver || x0_logs),
-                "keep sample: null argument");
-    LDM_REQUIRE(nsteps >= 0, "keep sample: negative step count");
-    LDM_REQUIRE(S5 >= 0 && S6 >= 0, "keep sample: negative key count");
-    const bool guided = s5_base || s6_base || guide_scale;
-    if (guided) LDM_TRY(guided_args_ok(s, s5_base, s6_base, guide_scale, S5, S6));
-    else LDM_REQUIRE(!key_bias5_base && !key_bias6_base, "keep sample: base key biases without a base style");
-    const bool any = z0 || n0 || keep || keep_coef;
-    LDM_REQUIRE(!any || (z0 && n0 && keep && keep_coef), "keep sample: z0, n0, keep and keep_coef go together (one is NULL)");
-    if (nsteps == 0) return 0;
-    if (any)
-        LDM_TRY(workspace_extent_ok(ldm_ddim_workspace_floats_keep(s, w, nsteps, S5, S6, guided), "ldm_ddim_workspace_floats_keep",
-                                    workspace, stream));
-    else if (guided) LDM_TRY(guided_workspace_ok(s, w, nsteps, S5, S6, workspace, stream));
-    const Guide g{s5_base, s6_base, key_bias5_base, key_bias6_base, guide_scale};
-    const Keep k{z0, n0, keep, keep_coef};
-    return sample_loop(s, w, x, s5, s6, t_table, coef_table, nsteps, eta, x0_logs, eps_logs, log_step_stride, workspace,
-                       stream, msolver, S5, S6, key_bias5, key_bias6, guided ? &g : nullptr, any ? &k : nullptr);
-}
-
-extern "C" int ldm_ddim_sample_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                                    const float* s6, const float* s5_base, const float* s6_base, int32_t S5, int32_t S6,
-                                    const float* key_bias5, const float* key_bias6, const float* key_bias5_base,
-                                    const float* key_bias6_base, const float* guide_scale, const float* z0,
-                                    const float* n0, const float* keep, const float* keep_coef, const int64_t* t_table,
-                                    const float* coef_table, int32_t nsteps, float eta, float* x0_logs, float* eps_logs,
-                                    int64_t log_step_stride, float* workspace, void* stream) {
-    return keep_sample(s, w, x, s5, s6, s5_base, s6_base, S5, S6, key_bias5, key_bias6, key_bias5_base, key_bias6_base,
-                       guide_scale, z0, n0, keep, keep_coef, t_table, coef_table, nsteps, eta, x0_logs, eps_logs,
-                       log_step_stride, workspace, stream, false);
-}
-
-extern "C" int ldm_msolver_sample_keep(const ldm_unet_shape* s, const ldm_unet_weights* w, float* x, const float* s5,
-                                       const float* s6, const float* s5_base, const float* s6_base, int32_t S5,
-                                       int32_t S6, const float* key_bias5, const float* key_bias6,
-                                       const float* key_bias5_base, const float* key_bias6_base,
-                                       const float* guide_scale, const float* z0, const float* n0, const float* keep,
-                                       const float* keep_coef, const int64_t* t_table, const float* coef_table,
-                                       int32_t nsteps, float* x0_logs, float* eps_logs, int64_t log_step_stride,
-                                       float* workspace, void* stream) {
-    return keep_sample(s, w, x, s5, s6, s5_base, s6_base, S5, S6, key_bias5, key_bias6, key_bias5_base, key_bias6_base,
-                       guide_scale, z0, n0, keep, keep_coef, t_table, coef_table, nsteps, 0.f, x0_logs, eps_logs,
-                       log_step_stride, workspace, stream, true);
+    LDM_REQUIRE(!keep || (a->z0 && a->n0 && a->keep && a->keep_coef),
+                "sample: z0, n0, keep and keep_coef go together (one is NULL)");
+    if (a->nsteps == 0) return 0;
+    LDM_TRY(workspace_extent_ok(ldm_sample_workspace_floats(s, w, a), a->workspace, a->stream));
+    const Guide g{a->s5_base, a->s6_base, a->key_bias5_base, a->key_bias6_base, a->guide_scale};
+    const Keep k{a->z0, a->n0, a->keep, a->keep_coef};
+    return sample_loop(s, w, a->x, a->s5, a->s6, a->t_table, a->coef_table, a->nsteps, msolver ? 0.f : a->eta, a->x0_logs,
+                       a->eps_logs, a->log_step_stride, a->workspace, a->stream, msolver, a->S5, a->S6, a->key_bias5,
+                       a->key_bias6, guided ? &g : nullptr, keep ? &k : nullptr);
 }

@@ -70,6 +70,20 @@ class UNetWeights(ctypes.Structure):
                 ("step_dtype", c_int32), ("step_bneck_w", c_fp)]
 
 
+SOLVER = {"ddim": 0, "msolver": 1}   # ldm_capi.h LDM_SOLVER_*
+
+
+class SampleArgs(ctypes.Structure):
+    """ldm_sample_args: the reverse loop's operands and options (NULL / 0 = off); semantics in ldm_capi.h."""
+    _fields_ = [("solver", c_int32), ("nsteps", c_int32), ("eta", c_float), ("S5", c_int32), ("S6", c_int32),
+                ("x", c_fp), ("s5", c_fp), ("s6", c_fp), ("key_bias5", c_fp), ("key_bias6", c_fp),
+                ("s5_base", c_fp), ("s6_base", c_fp), ("key_bias5_base", c_fp), ("key_bias6_base", c_fp),
+                ("guide_scale", c_fp),
+                ("z0", c_fp), ("n0", c_fp), ("keep", c_fp), ("keep_coef", c_fp),
+                ("t_table", c_vp), ("coef_table", c_fp), ("x0_logs", c_fp), ("eps_logs", c_fp),
+                ("log_step_stride", c_int64), ("workspace", c_fp), ("stream", c_vp)]
+
+
 ACT = {"none": 0, "relu": 1, "tanh": 2, "tanh_half": 3, "gelu": 4}
 DT_ROUND_OUT = 0x100   # ldm_epilogue.dtype flag (ldm_capi.h LDM_DT_ROUND_OUT); act codes: LDM_ACT_ROUND_* = dt << 8
 # 16-bit storage (ldm_capi.h): conv / wgrad dtype flags, and the BatchNorm / activation-backward act-code fields
@@ -192,47 +206,19 @@ SIGNATURES = {
     "ldm_loss_forward": (c_int32, [c_int32, c_fp, c_fp, c_int64, c_vp, c_fp, c_vp]),
     "ldm_loss_backward": (c_int32, [c_int32, c_fp, c_fp, c_int64, c_fp, c_fp, c_fp, c_vp]),
     "ldm_unet_workspace_floats": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights)]),
-    "ldm_ddim_workspace_floats": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_int32]),
     "ldm_unet_make_plans": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights)]),
     "ldm_unet_layer_desc": (c_int32, [ctypes.POINTER(UNetShape), c_int32, ctypes.POINTER(ConvDesc)]),
     "ldm_unet_forward": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_vp, c_int32,
                                    c_fp, c_fp, c_fp, c_fp, c_vp]),
-    "ldm_ddim_sample": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp, c_vp,
-                                  c_fp, c_int32, c_float, c_fp, c_fp, c_int64, c_fp, c_vp]),
-    "ldm_msolver_sample": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp, c_vp,
-                                     c_fp, c_int32, c_fp, c_fp, c_int64, c_fp, c_vp]),
-    # style mixing (stylemix.hip, unet.hip): key-tiled folded attention with a key bias, and the loops over S5 / S6 keys
+    "ldm_sample_workspace_floats": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights),
+                                              ctypes.POINTER(SampleArgs)]),
+    "ldm_sample": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), ctypes.POINTER(SampleArgs)]),
+    # style mixing (stylemix.hip): key-tiled folded attention with a key bias
     "ldm_attention_folded_keys": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_int32, c_int32,
                                             c_int32, c_vp]),
     "ldm_attention_fold_keys_bias": (c_int32, [c_fp, c_fp, c_fp, c_int32, c_int32, c_int32, c_int32, c_float, c_fp,
                                                c_fp, c_fp, c_vp]),
-    "ldm_ddim_workspace_floats_mix": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_int32,
-                                                c_int32, c_int32]),
-    "ldm_ddim_sample_mix": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
-                                      c_int32, c_int32, c_fp, c_fp, c_vp, c_fp, c_int32, c_float, c_fp, c_fp, c_int64,
-                                      c_fp, c_vp]),
-    "ldm_msolver_sample_mix": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
-                                         c_int32, c_int32, c_fp, c_fp, c_vp, c_fp, c_int32, c_fp, c_fp, c_int64, c_fp,
-                                         c_vp]),
-    # style guidance: target and base maps, their key biases, a per-sample scale
-    "ldm_ddim_workspace_floats_guided": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_int32,
-                                                   c_int32, c_int32]),
-    "ldm_ddim_sample_guided": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
-                                         c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_vp, c_fp,
-                                         c_int32, c_float, c_fp, c_fp, c_int64, c_fp, c_vp]),
-    "ldm_msolver_sample_guided": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
-                                            c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_vp, c_fp,
-                                            c_int32, c_fp, c_fp, c_int64, c_fp, c_vp]),
     "ldm_guide_eps": (c_int32, [c_fp, c_fp, c_fp, c_int64, c_int32, c_fp, c_vp]),
-    # regional keep: the guided entries' list plus z0, n0, keep, keep_coef
-    "ldm_ddim_workspace_floats_keep": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_int32,
-                                                 c_int32, c_int32, c_int32]),
-    "ldm_ddim_sample_keep": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
-                                       c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                       c_vp, c_fp, c_int32, c_float, c_fp, c_fp, c_int64, c_fp, c_vp]),
-    "ldm_msolver_sample_keep": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), c_fp, c_fp, c_fp,
-                                          c_fp, c_fp, c_int32, c_int32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                          c_fp, c_vp, c_fp, c_int32, c_fp, c_fp, c_int64, c_fp, c_vp]),
     "ldm_keep_blend": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_int64, c_vp]),
     # backward / optimiser
     "ldm_conv_tiled_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),

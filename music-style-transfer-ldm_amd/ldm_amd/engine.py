@@ -1,5 +1,5 @@
 """UNet engine: binds a UNet module's parameters to the C ABI's ldm_unet_weights and runs the whole
-denoiser (ldm_unet_forward) or the whole reverse loop (ldm_ddim_sample) in one C call each; the
+denoiser (ldm_unet_forward) or the whole reverse loop (ldm_sample) in one C call each; the
 reverse loop is replayed from a captured hipGraph (torch.cuda.CUDAGraph on the same stream).
 
 Host side only: it owns workspaces (torch allocations) and caches, never computes.
@@ -197,45 +197,24 @@ class UNetEngine:
     def workspace(self, shape, device, nsteps=0, slot=0, keys=None, guided=False, plan_batch=None, keep=False):
         """Workspace for this shape and its bound plans; `slot` separates concurrently running sub-batch
         chains.  Zero-filled on allocation: it carries the split-K tile counters (ldm_capi.h).
-        keys = (S5, S6): the style-mixing loops' workspace for those key counts (a buffer of its own).
-        guided: the guided loops' workspace for the caller's `shape` (sized by the guided function for the doubled
-        batch the body runs at; a buffer of its own; keys (0, 0) = the maps' own counts; plan_batch as in
-        _guided_weights).
-        keep: the regional-keep loops' workspace (ldm_ddim_workspace_floats_keep), guided or not; a buffer of its own."""
+        keys = (S5, S6): the style-mixing loops' key counts (None or 0 = the maps' own).
+        guided: the guided loops' workspace for the caller's `shape` (sized for the doubled batch the body runs at;
+        plan_batch as in _guided_weights).
+        keep: with the regional keep's region.
+        One buffer per configuration (ldm_sample_workspace_floats of it) and slot."""
+        own = ((shape.H // 4) * (shape.W // 4), (shape.H // 8) * (shape.W // 8))
+        keys = tuple(0 if int(k) == o else int(k) for k, o in zip(keys, own)) if keys else (0, 0)
+        plan_batch = (plan_batch or 0) if guided else 0
+        w = self._guided_weights(shape.B, shape.C, shape.H, shape.W, plan_batch) if guided else self.weights(shape)
+        a = L.SampleArgs(nsteps=int(nsteps), S5=keys[0], S6=keys[1])
+        if guided:   # (the size function reads only whether an option's pointers are set)
+            a.s5_base = a.s6_base = a.guide_scale = 1
         if keep:
-            w = self._guided_weights(shape.B, shape.C, shape.H, shape.W, plan_batch) if guided else self.weights(shape)
-            keys = tuple(keys) if keys else (0, 0)
-            n = L.load().ldm_ddim_workspace_floats_keep(byref(shape), byref(w), int(nsteps), int(keys[0]), int(keys[1]),
-                                                        1 if guided else 0)
-            if n <= 0:
-                raise RuntimeError("ldm_ddim_workspace_floats_keep failed")
-            key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot, "keep", bool(guided),
-                   plan_batch or 0) + keys
-            ws = self._ws.get(key)
-            if ws is None or ws.numel() < n:
-                ws = torch.zeros(int(n), device=device, dtype=torch.float32)
-                self._ws[key] = ws
-            return ws
-        if guided:
-            w = self._guided_weights(shape.B, shape.C, shape.H, shape.W, plan_batch)
-            keys = tuple(keys) if keys else (0, 0)
-            n = L.load().ldm_ddim_workspace_floats_guided(byref(shape), byref(w), int(nsteps), int(keys[0]), int(keys[1]))
-            if n <= 0:
-                raise RuntimeError("ldm_ddim_workspace_floats_guided failed")
-            key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot, "guided", plan_batch or 0) + keys
-            ws = self._ws.get(key)
-            if ws is None or ws.numel() < n:
-                ws = torch.zeros(int(n), device=device, dtype=torch.float32)
-                self._ws[key] = ws
-            return ws
-        w = self.weights(shape)
-        if keys is None:
-            n = L.load().ldm_ddim_workspace_floats(byref(shape), byref(w), int(nsteps))
-        else:
-            n = L.load().ldm_ddim_workspace_floats_mix(byref(shape), byref(w), int(nsteps), int(keys[0]), int(keys[1]))
+            a.z0 = a.n0 = a.keep = a.keep_coef = 1
+        n = L.load().ldm_sample_workspace_floats(byref(shape), byref(w), byref(a))
         if n <= 0:
-            raise RuntimeError("ldm_ddim_workspace_floats failed")
-        key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot) + (tuple(keys) if keys else ())
+            raise RuntimeError("ldm_sample_workspace_floats failed")
+        key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot, keys, bool(guided), plan_batch, bool(keep))
         ws = self._ws.get(key)
         if ws is None or ws.numel() < n:
             ws = torch.zeros(int(n), device=device, dtype=torch.float32)
@@ -402,8 +381,8 @@ class UNetEngine:
         return cls.KeepOperands(v.detach().to(device, torch.float32).contiguous() for v in (z0, n0, wf, coefs))
 
     def _guided_operands(self, x, s5, s6, key_bias5, key_bias6, base, scale):
-        """The guided C entries' operands checked: (S5, S6, (s5_base, s6_base, S5, S6, key_bias5, key_bias6,
-        key_bias5_base, key_bias6_base, scale) as pointers)."""
+        """The guided loop's operands checked: its SampleArgs fields (the key counts, and the biases, the base maps and
+        the scale as pointers)."""
         B, C, H, W = x.shape
         s5b, s6b, kb5b, kb6b = base
         ops.require_device(s5b, s6b, scale, what="guidance operand")
@@ -421,7 +400,8 @@ class UNetEngine:
             _, _, p5b, p6b = self._mix_check(x, s5b, s6b, kb5b, kb6b)
         else:
             self._single_maps_check(x, s5, s6)
-        return S5, S6, (s5b.data_ptr(), s6b.data_ptr(), S5, S6, p5, p6, p5b, p6b, scale.data_ptr())
+        return dict(S5=S5, S6=S6, key_bias5=p5, key_bias6=p6, s5_base=s5b.data_ptr(), s6_base=s6b.data_ptr(),
+                    key_bias5_base=p5b, key_bias6_base=p6b, guide_scale=scale.data_ptr())
 
     @staticmethod
     def _single_maps_check(x, s5, s6):
@@ -430,101 +410,35 @@ class UNetEngine:
             raise RuntimeError(f"UNet: style maps must be s5 [B,256,H/4,W/4], s6 [B,512,H/8,W/8] for z {tuple(x.shape)}; "
                                f"got {tuple(s5.shape)}, {tuple(s6.shape)}")
 
-    def _keep_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5,
-                   key_bias6, base, scale, plan_batch, kp):
-        """One C loop with the regional keep (ldm_*_sample_keep), guided (base / scale as in _guided_call) or not."""
+    def _sample_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
+                     key_bias5=None, key_bias6=None, base=None, scale=None, plan_batch=None, keep=None):
+        """One C loop (ldm_sample) of solver "ddim" / "msolver" on x, with whichever options are given: a mix (stacked
+        s5 / s6, key biases), guidance (base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the target's key
+        counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights) and the regional
+        keep (keep_operands())."""
         B, C, H, W = x.shape
         shape = self.shape(B, C, H, W)
         n = t_table.shape[0]
-        guided = base is not None
-        if guided:
-            S5, S6, gargs = self._guided_operands(x, s5, s6, key_bias5, key_bias6, base, scale)
-            w = self._guided_weights(B, C, H, W, plan_batch)
+        a = L.SampleArgs(solver=L.SOLVER[solver], nsteps=n, eta=float(eta), x=x.data_ptr(), s5=s5.data_ptr(),
+                         s6=s6.data_ptr(), t_table=t_table.data_ptr(), coef_table=coef_table.data_ptr(),
+                         x0_logs=ops._p(x0_logs), eps_logs=ops._p(eps_logs), log_step_stride=int(log_stride),
+                         stream=ops.stream_handle())
+        if base is not None:
+            for f, v in self._guided_operands(x, s5, s6, key_bias5, key_bias6, base, scale).items():
+                setattr(a, f, v)
+            w = self._guided_weights(B, C, H, W, plan_batch)   # the body runs at the doubled batch: targets, then bases
         else:
-            S5, S6, p5, p6 = 0, 0, None, None
             if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
-                S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
+                a.S5, a.S6, a.key_bias5, a.key_bias6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
             else:
                 self._single_maps_check(x, s5, s6)
             w = self.weights(shape)
-            gargs = (None, None, S5, S6, p5, p6, None, None, None)
-        kp = self.keep_operands(kp, x.shape, n, x.device)
-        ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6), guided=guided, plan_batch=plan_batch, keep=True)
-        head = (byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr()) + gargs + \
-            tuple(v.data_ptr() for v in kp) + (t_table.data_ptr(), coef_table.data_ptr(), n)
-        tail = (ops._p(eps_logs), int(log_stride), ws.data_ptr(), ops.stream_handle())
-        if solver == "msolver":
-            L.call("ldm_msolver_sample_keep", *head, x0_logs.data_ptr(), *tail)
-        else:
-            L.call("ldm_ddim_sample_keep", *head, float(eta), ops._p(x0_logs), *tail)
-
-    def _guided_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5,
-                     key_bias6, base, scale, plan_batch=None):
-        """One guided C loop (ldm_*_sample_guided): base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the
-        target's key counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights."""
-        B, C, H, W = x.shape
-        shape = self.shape(B, C, H, W)
-        n = t_table.shape[0]
-        S5, S6, gargs = self._guided_operands(x, s5, s6, key_bias5, key_bias6, base, scale)
-        w = self._guided_weights(B, C, H, W, plan_batch)   # the body runs at the doubled batch: targets, then bases
-        ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6), guided=True, plan_batch=plan_batch)
-        head = (byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr()) + gargs + \
-            (t_table.data_ptr(), coef_table.data_ptr(), n)
-        tail = (ops._p(eps_logs), int(log_stride), ws.data_ptr(), ops.stream_handle())
-        if solver == "msolver":
-            L.call("ldm_msolver_sample_guided", *head, x0_logs.data_ptr(), *tail)
-        else:
-            L.call("ldm_ddim_sample_guided", *head, float(eta), ops._p(x0_logs), *tail)
-
-    def _ddim_call(self, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot, key_bias5=None,
-                   key_bias6=None, base=None, scale=None, plan_batch=None, kp=None):
-        if kp is not None:
-            return self._keep_call("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
-                                   key_bias5, key_bias6, base, scale, plan_batch, kp)
-        if base is not None:
-            return self._guided_call("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
-                                     key_bias5, key_bias6, base, scale, plan_batch)
-        B, C, H, W = x.shape
-        shape = self.shape(B, C, H, W)
-        n = t_table.shape[0]
-        if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
-            S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
-            w = self.weights(shape)
-            ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6))
-            L.call("ldm_ddim_sample_mix", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(), S5, S6,
-                   p5, p6, t_table.data_ptr(), coef_table.data_ptr(), n, float(eta), ops._p(x0_logs), ops._p(eps_logs),
-                   int(log_stride), ws.data_ptr(), ops.stream_handle())
-            return
-        w = self.weights(shape)
-        ws = self.workspace(shape, x.device, n, slot)
-        L.call("ldm_ddim_sample", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(),
-               t_table.data_ptr(), coef_table.data_ptr(), n, float(eta), ops._p(x0_logs), ops._p(eps_logs),
-               int(log_stride), ws.data_ptr(), ops.stream_handle())
-
-    def _msolver_call(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs, log_stride, slot, key_bias5=None,
-                      key_bias6=None, base=None, scale=None, plan_batch=None, kp=None):
-        if kp is not None:
-            return self._keep_call("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, log_stride, slot,
-                                   key_bias5, key_bias6, base, scale, plan_batch, kp)
-        if base is not None:
-            return self._guided_call("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, log_stride, slot,
-                                     key_bias5, key_bias6, base, scale, plan_batch)
-        B, C, H, W = x.shape
-        shape = self.shape(B, C, H, W)
-        n = t_table.shape[0]
-        if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
-            S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
-            w = self.weights(shape)
-            ws = self.workspace(shape, x.device, n, slot, keys=(S5, S6))
-            L.call("ldm_msolver_sample_mix", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(), S5, S6,
-                   p5, p6, t_table.data_ptr(), coef_table.data_ptr(), n, x0_logs.data_ptr(), ops._p(eps_logs),
-                   int(log_stride), ws.data_ptr(), ops.stream_handle())
-            return
-        w = self.weights(shape)
-        ws = self.workspace(shape, x.device, n, slot)
-        L.call("ldm_msolver_sample", byref(shape), byref(w), x.data_ptr(), s5.data_ptr(), s6.data_ptr(),
-               t_table.data_ptr(), coef_table.data_ptr(), n, x0_logs.data_ptr(), ops._p(eps_logs), int(log_stride),
-               ws.data_ptr(), ops.stream_handle())
+        if keep is not None:
+            keep = self.keep_operands(keep, x.shape, n, x.device)
+            a.z0, a.n0, a.keep, a.keep_coef = (v.data_ptr() for v in keep)
+        a.workspace = self.workspace(shape, x.device, n, slot, keys=(a.S5, a.S6), guided=base is not None,
+                                     plan_batch=plan_batch, keep=keep is not None).data_ptr()
+        L.call("ldm_sample", byref(shape), byref(w), byref(a))
 
     def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None, key_bias5=None,
                      key_bias6=None, base=None, guidance_scale=1.0, keep=None):
@@ -536,11 +450,8 @@ class UNetEngine:
         if coef_table.dim() != 2 or coef_table.shape[1] != 8 or coef_table.shape[0] != t_table.shape[0]:
             raise ValueError(f"msolver_loop: coef_table must be [n,8] for n = {t_table.shape[0]} steps, "
                              f"got {tuple(coef_table.shape)}")
-        return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
-                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None, base=None, scale=None, pb=None,
-                          kp=None:
-                          self._msolver_call(xs, a5, a6, t, coef_table, x0l, epl, stride, slot, b5, b6, base, scale, pb, kp),
-                          key_bias5, key_bias6, base, guidance_scale, keep)
+        return self._loop("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, split, plan, key_bias5,
+                          key_bias6, base, guidance_scale, keep)
 
     def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None,
                   key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None):
@@ -568,117 +479,75 @@ class UNetEngine:
         The path is per-sample, so the result is the same up to fp32 summation order (a sub-batch
         size may get a conv plan that splits K differently); the chains' launch and memory latencies
         overlap each other's work."""
-        return self._loop(x, s5, s6, t_table, x0_logs, eps_logs, split, plan,
-                          lambda xs, a5, a6, t, x0l, epl, stride, slot, b5=None, b6=None, base=None, scale=None, pb=None,
-                          kp=None:
-                          self._ddim_call(xs, a5, a6, t, coef_table, eta, x0l, epl, stride, slot, b5, b6, base, scale, pb, kp),
-                          key_bias5, key_bias6, base, guidance_scale, keep)
+        return self._loop("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, split, plan, key_bias5,
+                          key_bias6, base, guidance_scale, keep)
 
-    def _loop(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5=None, key_bias6=None, base=None,
-              guidance_scale=1.0, keep=None):
-        """The whole batch in one C call, or one per sub-batch chain; call(x, s5, s6, t, x0_logs, eps_logs,
-        log_stride, slot[, key_bias5, key_bias6[, base, scale, plan_batch, keep]]) is one sampler's C call.  The keep
-        operands are sliced with the batch."""
-        B = x.shape[0]
+    def _loop(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, split, plan, key_bias5=None,
+              key_bias6=None, base=None, guidance_scale=1.0, keep=None):
+        """The whole batch in one _sample_call, or one per sub-batch chain with every per-sample operand (the maps, the
+        biases, the base, the scales, the keep operands, the logs) sliced with the batch.
+        Guided, on the step-kernel path, the chains run the whole batch's plans (_guided_weights), so split > 1 gives
+        each sample bitwise what split = 1 gives it while both select the same per-batch forms (the bottleneck value
+        fold applies up to a doubled batch of 8)."""
+        B, n = x.shape[0], t_table.shape[0]
+        guided = base is not None
         if keep is not None:
-            keep = self.keep_operands(keep, x.shape, t_table.shape[0], x.device)
-        if base is not None:
-            return self._loop_guided(x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5, key_bias6,
-                                     base, guidance_scale, keep)
-        if not self.is_unguided(None, guidance_scale):
-            raise ValueError("guidance_scale other than 1 needs a base style to guide against (base=)")
-        keys = self.mix_keys(x, s5, s6, key_bias5, key_bias6)
-        if keys is not None:
-            self._mix_check(x, s5, s6, key_bias5, key_bias6)
+            keep = self.keep_operands(keep, x.shape, n, x.device)
+        scale = None
+        if guided:
+            if len(base) != 4:
+                raise ValueError("base must be (s5_base, s6_base, key_bias5_base, key_bias6_base)")
+            scale = guidance_scale
+            if not (isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and
+                    tuple(scale.shape) == (B,) and scale.is_contiguous()):   # (a graph's static buffer is passed as it is)
+                scale = self.guidance_scale(scale, B, x.device)
+            base = (ops.f32c(base[0]), ops.f32c(base[1]), base[2], base[3])
+        else:
+            if not self.is_unguided(None, guidance_scale):
+                raise ValueError("guidance_scale other than 1 needs a base style to guide against (base=)")
+            if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
+                self._mix_check(x, s5, s6, key_bias5, key_bias6)
         if plan is None:
             plan = self.split_plan(t_table, B, split) if split > 1 else None
         if not plan or len(plan) == 1:
-            if keep is not None:
-                call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6, None, None, None, keep)
-            elif keys is None:
-                call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0)
-            else:
-                call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6)
+            self._sample_call(solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6,
+                              base, scale, None, keep)
             return x
         per_step = x[0].numel() * B
         main = torch.cuda.current_stream(x.device)
         streams = self.side_streams(x.device, len(plan))
         C, H, W = x.shape[1:]
+        keys = self._guided_keys(x, s5, s6, key_bias5, key_bias6, base) if guided else \
+            self.mix_keys(x, s5, s6, key_bias5, key_bias6)
         for k, (lo, hi, t_sub) in enumerate(plan):   # bind / pack / allocate on the main stream first
-            shape = self.shape(hi - lo, C, H, W)
-            self.weights(shape)
-            self.workspace(shape, x.device, t_table.shape[0], k, keys=keys, keep=keep is not None)
+            self.workspace(self.shape(hi - lo, C, H, W), x.device, n, k, keys=keys, guided=guided,
+                           plan_batch=B if guided else None, keep=keep is not None)
+
+        def cut(lo, hi):
+            """(x, s5, s6, x0_logs, eps_logs, key_bias5, key_bias6, base, scale, keep) of samples [lo, hi)"""
+            def c(v):
+                return None if v is None else v[lo:hi]
+            return (x[lo:hi], s5[lo:hi], s6[lo:hi], None if x0_logs is None else x0_logs[0, lo:hi],
+                    None if eps_logs is None else eps_logs[0, lo:hi], c(key_bias5), c(key_bias6),
+                    tuple(c(v) for v in base) if guided else None, c(scale), self._keep_cut(keep, lo, hi))
+
         for k, (lo, hi, t_sub) in enumerate(plan):
             st = streams[k]
             st.wait_stream(main)
             if not torch.cuda.is_current_stream_capturing():
                 t_sub.record_stream(st)
             with torch.cuda.stream(st):
-                x0l = None if x0_logs is None else x0_logs[0, lo:hi]
-                epl = None if eps_logs is None else eps_logs[0, lo:hi]
-                if keep is not None:
-                    call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, x0l, epl, per_step, k,
-                         None if key_bias5 is None else key_bias5[lo:hi], None if key_bias6 is None else key_bias6[lo:hi],
-                         None, None, None, self._keep_cut(keep, lo, hi))
-                elif keys is None:
-                    call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, x0l, epl, per_step, k)
-                else:   # the biases are split with the maps (leading-dimension slices stay contiguous)
-                    call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, x0l, epl, per_step, k,
-                         None if key_bias5 is None else key_bias5[lo:hi],
-                         None if key_bias6 is None else key_bias6[lo:hi])
+                xs, a5, a6, x0l, epl, b5, b6, gb, gs, kc = cut(lo, hi)
+                self._sample_call(solver, xs, a5, a6, t_sub, coef_table, eta, x0l, epl, per_step, k, b5, b6, gb, gs,
+                                  B if guided else None, kc)
         for st in streams:
             main.wait_stream(st)
         return x
-
 
     @classmethod
     def _keep_cut(cls, kp, lo, hi):
         """A sub-batch chain's slice of the keep operands (the coefficient table is shared)."""
         return None if kp is None else cls.KeepOperands((kp[0][lo:hi], kp[1][lo:hi], kp[2][lo:hi], kp[3]))
-
-    def _loop_guided(self, x, s5, s6, t_table, x0_logs, eps_logs, split, plan, call, key_bias5, key_bias6, base, scale,
-                     kp=None):
-        """_loop for a guided sampler: the base maps, their biases and the scales are sliced with the batch.  On the
-        step-kernel path the sub-batch chains run the whole batch's plans (_guided_weights), so split > 1 gives each
-        sample bitwise what split = 1 gives it while both select the same per-batch forms (the bottleneck value
-        fold applies up to a doubled batch of 8)."""
-        B = x.shape[0]
-        if len(base) != 4:
-            raise ValueError("base must be (s5_base, s6_base, key_bias5_base, key_bias6_base)")
-        if not (isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and
-                tuple(scale.shape) == (B,) and scale.is_contiguous()):   # (a graph's static buffer is passed as it is)
-            scale = self.guidance_scale(scale, B, x.device)
-        base = (ops.f32c(base[0]), ops.f32c(base[1]), base[2], base[3])
-        if plan is None:
-            plan = self.split_plan(t_table, B, split) if split > 1 else None
-        if not plan or len(plan) == 1:
-            call(x, s5, s6, t_table, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6, base, scale, None, kp)
-            return x
-        per_step = x[0].numel() * B
-        main = torch.cuda.current_stream(x.device)
-        streams = self.side_streams(x.device, len(plan))
-        C, H, W = x.shape[1:]
-        keys = self._guided_keys(x, s5, s6, key_bias5, key_bias6, base)
-        for k, (lo, hi, t_sub) in enumerate(plan):   # bind / pack / allocate on the main stream first
-            self.workspace(self.shape(hi - lo, C, H, W), x.device, t_table.shape[0], k, keys=keys, guided=True,
-                           plan_batch=B, keep=kp is not None)
-
-        def cut(v, lo, hi):
-            return None if v is None else v[lo:hi]
-
-        for k, (lo, hi, t_sub) in enumerate(plan):
-            st = streams[k]
-            st.wait_stream(main)
-            if not torch.cuda.is_current_stream_capturing():
-                t_sub.record_stream(st)
-            with torch.cuda.stream(st):
-                call(x[lo:hi], s5[lo:hi], s6[lo:hi], t_sub, None if x0_logs is None else x0_logs[0, lo:hi],
-                     None if eps_logs is None else eps_logs[0, lo:hi], per_step, k, cut(key_bias5, lo, hi),
-                     cut(key_bias6, lo, hi), tuple(cut(v, lo, hi) for v in base), scale[lo:hi], B,
-                     self._keep_cut(kp, lo, hi))
-        for st in streams:
-            main.wait_stream(st)
-        return x
 
 
 class GraphedDDIM:
@@ -752,13 +621,9 @@ class GraphedDDIM:
                 gb = None if self.base is None else tuple(None if v is None else v[lo:hi] for v in self.base)
                 gs = None if self.scale is None else self.scale[lo:hi]
                 kc = engine._keep_cut(self.keep, lo, hi)
-                if solver == "msolver":
-                    engine._msolver_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, x0l, epl,
-                                         per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None, kc)
-                else:
-                    engine._ddim_call(self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
-                                      x0l, epl, per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None,
-                                      kc)
+                engine._sample_call(solver, self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
+                                    x0l, epl, per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None,
+                                    kc)
             self.graphs.append(g)
 
     def _run(self, plan=None):

@@ -437,7 +437,7 @@ class LDM(nn.Module):
         base_embedding / guidance_scale (a finite float or one per sample, [B]): style guidance.  Each step
         evaluates the denoiser under both embeddings on the same x and t and steps on eps = e_b + s (e_t - e_b)
         (fp32, one rounding per operation); the logs hold the guided x0 / eps.  Without a base and at scale 1 the
-        calls below are the unguided ones, argument for argument.
+        loop below is the unguided one.
 
         keep = (z0, n0, w, coefs): the regional keep (UNetEngine.ddim_loop).  After each step's update the state is
         blended with coefs[i][0] z0 + coefs[i][1] n0 under the weights w [B,H,W]; the logs stay unblended."""
@@ -483,19 +483,15 @@ class LDM(nn.Module):
             guide = {"base": base, "guidance_scale": scale}
         if keep is not None:
             guide["keep"] = keep
+        if mix or guide:    # (the plain call stays the positional one)
+            guide.update(key_bias5=kb5, key_bias6=kb6)
         with torch.no_grad():
-            if UNetEngine.supports(x.shape[1]) and (mix or guided or keep is not None):
+            if UNetEngine.supports(x.shape[1]):
                 eng = engine_for(self.unet)
                 if order:
-                    eng.msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs, key_bias5=kb5, key_bias6=kb6, **guide)
+                    eng.msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs, **guide)
                 else:
-                    eng.ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs, key_bias5=kb5,
-                                  key_bias6=kb6, **guide)
-            elif UNetEngine.supports(x.shape[1]):
-                if order:
-                    engine_for(self.unet).msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs)
-                else:
-                    engine_for(self.unet).ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs)
+                    eng.ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs, **guide)
             else:   # latent widths the fused engine does not take: per-layer UNet + the update kernel
                 if mix:
                     raise RuntimeError(f"style mix: latent width {x.shape[1]} runs the per-layer path, which takes one "

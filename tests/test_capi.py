@@ -36,15 +36,16 @@ def test_struct_layout_matches_c(tmp_path):
     from ldm_amd import _lib as L
     probe = tmp_path / "probe.c"
     probe.write_text(f'#include "{HEADER}"\n#include <stdio.h>\n#include <stddef.h>\n'
-                     "int main(void){printf(\"%zu %zu %zu %zu %zu %zu %zu\\n\", sizeof(ldm_conv_desc), "
+                     "int main(void){printf(\"%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n\", sizeof(ldm_conv_desc), "
                      "sizeof(ldm_epilogue), sizeof(ldm_conv_plan), sizeof(ldm_unet_shape), sizeof(ldm_unet_weights), "
-                     "offsetof(ldm_unet_weights, ca_wq), offsetof(ldm_unet_weights, t_freqs)); return 0;}\n")
+                     "offsetof(ldm_unet_weights, ca_wq), offsetof(ldm_unet_weights, t_freqs), sizeof(ldm_sample_args), "
+                     "offsetof(ldm_sample_args, x), offsetof(ldm_sample_args, stream)); return 0;}\n")
     exe = tmp_path / "probe"
     subprocess.run(["gcc", str(probe), "-o", str(exe)], check=True)
     got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
     want = [ctypes.sizeof(L.ConvDesc), ctypes.sizeof(L.Epilogue), ctypes.sizeof(L.ConvPlan),
             ctypes.sizeof(L.UNetShape), ctypes.sizeof(L.UNetWeights), L.UNetWeights.ca_wq.offset,
-            L.UNetWeights.t_freqs.offset]
+            L.UNetWeights.t_freqs.offset, ctypes.sizeof(L.SampleArgs), L.SampleArgs.x.offset, L.SampleArgs.stream.offset]
     assert got == want
 
 

@@ -396,7 +396,11 @@ def test_c_abi_errors(ctx, cuda):
     w = eng.weights(eng.shape(2 * B, 32, H, W))
     ws = eng.workspace(shape, cuda, STEPS, guided=True)
     assert ws.numel() > eng.workspace(shape, cuda, STEPS).numel()
-    assert L.load().ldm_ddim_workspace_floats_guided(ctypes.byref(shape), ctypes.byref(w), -1, 0, 0) < 0
+
+    def size(wts, **fields):
+        return int(L.load().ldm_sample_workspace_floats(ctypes.byref(shape), ctypes.byref(wts), ctypes.byref(L.SampleArgs(**fields))))
+
+    assert size(w, nsteps=-1, s5_base=1, s6_base=1, guide_scale=1) < 0
     x = z.to(cuda).clone()
     d = [t.to(cuda) for t in (*tgt, *base)]
     tt = torch.from_numpy(ctx["times"])
@@ -405,44 +409,55 @@ def test_c_abi_errors(ctx, cuda):
     scale = torch.ones(B, device=cuda)
     x0l = torch.empty((STEPS,) + tuple(z.shape), device=cuda)
 
-    def call(name, s5b, s6b, sc, coef, *mid):
-        L.call(name, ctypes.byref(shape), ctypes.byref(w), x.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), s5b, s6b, 0, 0,
-               None, None, None, None, sc, t_table.data_ptr(), coef.data_ptr(), STEPS, *mid, None, 0, ws.data_ptr(),
-               ops.stream_handle())
+    def call(solver, s5b, s6b, sc, coef, wsp=None, wts=w):
+        a = L.SampleArgs(solver=L.SOLVER[solver], nsteps=STEPS, eta=0.0, x=x.data_ptr(), s5=d[0].data_ptr(),
+                         s6=d[1].data_ptr(), s5_base=s5b, s6_base=s6b, guide_scale=sc, t_table=t_table.data_ptr(),
+                         coef_table=coef.data_ptr(), x0_logs=x0l.data_ptr(), workspace=wsp or ws.data_ptr(),
+                         stream=ops.stream_handle())
+        L.call("ldm_sample", ctypes.byref(shape), ctypes.byref(wts), ctypes.byref(a))
 
     c4, c8 = fd.reverse_coefs(tt).to(cuda), fd.multistep_coefs(tt).to(cuda)
-    for name, coef, mid in (("ldm_ddim_sample_guided", c4, (0.0, x0l.data_ptr())),
-                            ("ldm_msolver_sample_guided", c8, (x0l.data_ptr(),))):
+    for name, coef in (("ddim", c4), ("msolver", c8)):
         with pytest.raises(L.LDMError, match="base"):
-            call(name, None, d[3].data_ptr(), scale.data_ptr(), coef, *mid)
+            call(name, None, d[3].data_ptr(), scale.data_ptr(), coef)
         with pytest.raises(L.LDMError, match="base"):
-            call(name, d[2].data_ptr(), None, scale.data_ptr(), coef, *mid)
+            call(name, d[2].data_ptr(), None, scale.data_ptr(), coef)
         with pytest.raises(L.LDMError, match="scale"):
-            call(name, d[2].data_ptr(), d[3].data_ptr(), None, coef, *mid)
+            call(name, d[2].data_ptr(), d[3].data_ptr(), None, coef)
     with pytest.raises(L.LDMError):
         L.call("ldm_guide_eps", x.data_ptr(), x.data_ptr(), None, 16, B, x.data_ptr(), ops.stream_handle())
-    # a workspace sized by the unguided function, as an allocation of its own (the entries ask the runtime for the
+    # a workspace sized for the unguided loop, as an allocation of its own (the entry asks the runtime for the
     # extent of the allocation that holds the pointer; torch's caching allocator would hand out part of a larger one)
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipMalloc.argtypes, hip.hipMalloc.restype = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t], ctypes.c_int
     hip.hipFree.argtypes, hip.hipFree.restype = [ctypes.c_void_p], ctypes.c_int
-    n_small = int(L.load().ldm_ddim_workspace_floats(ctypes.byref(shape), ctypes.byref(eng.weights(shape)), STEPS))
+    w1 = eng.weights(shape)
+    n_small = size(w1, nsteps=STEPS)
     assert 0 < n_small < ws.numel()
     short = ctypes.c_void_p()
     assert hip.hipMalloc(ctypes.byref(short), n_small * 4) == 0
     try:
-        for name, coef, mid in (("ldm_ddim_sample_guided", c4, (0.0, x0l.data_ptr())),
-                                ("ldm_msolver_sample_guided", c8, (x0l.data_ptr(),))):
+        for name, coef in (("ddim", c4), ("msolver", c8)):
             with pytest.raises(L.LDMError, match="workspace"):
-                L.call(name, ctypes.byref(shape), ctypes.byref(w), x.data_ptr(), d[0].data_ptr(), d[1].data_ptr(),
-                       d[2].data_ptr(), d[3].data_ptr(), 0, 0, None, None, None, None, scale.data_ptr(), t_table.data_ptr(),
-                       coef.data_ptr(), STEPS, *mid, None, 0, short.value, ops.stream_handle())
+                call(name, d[2].data_ptr(), d[3].data_ptr(), scale.data_ptr(), coef, short.value)
+    finally:
+        torch.cuda.synchronize()
+        assert hip.hipFree(short) == 0
+    # the plain loop (no base, no keep) is held to its size too: one float short is an error, not an overrun
+    assert hip.hipMalloc(ctypes.byref(short), (n_small - 1) * 4) == 0
+    try:
+        with pytest.raises(L.LDMError, match="workspace"):
+            call("ddim", None, None, None, c4, short.value, w1)
     finally:
         torch.cuda.synchronize()
         assert hip.hipFree(short) == 0
     torch.cuda.synchronize()
     assert torch.equal(x.cpu(), z)          # nothing ran
-    # the good call still works afterwards
-    call("ldm_ddim_sample_guided", d[2].data_ptr(), d[3].data_ptr(), scale.data_ptr(), c4, 0.0, x0l.data_ptr())
+    # the good calls still work afterwards: the plain one on a workspace of its size, then the guided one
+    call("ddim", None, None, None, c4, eng.workspace(shape, cuda, STEPS).data_ptr(), w1)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(x).all()) and not torch.equal(x.cpu(), z)
+    x.copy_(z.to(cuda))
+    call("ddim", d[2].data_ptr(), d[3].data_ptr(), scale.data_ptr(), c4)
     torch.cuda.synchronize()
     assert bool(torch.isfinite(x).all()) and not torch.equal(x.cpu(), z)

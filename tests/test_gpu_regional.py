@@ -403,10 +403,13 @@ def test_c_abi_errors(ctx, cuda):
     shape = eng.shape(B, 32, H, W)
     w = eng.weights(shape)
     ws = eng.workspace(shape, cuda, STEPS, keep=True)
-    n_plain = int(L.load().ldm_ddim_workspace_floats(ctypes.byref(shape), ctypes.byref(w), STEPS))
-    n_keep = int(L.load().ldm_ddim_workspace_floats_keep(ctypes.byref(shape), ctypes.byref(w), STEPS, 0, 0, 0))
+
+    def size(**fields):
+        return int(L.load().ldm_sample_workspace_floats(ctypes.byref(shape), ctypes.byref(w), ctypes.byref(L.SampleArgs(**fields))))
+
+    n_plain, n_keep = size(nsteps=STEPS), size(nsteps=STEPS, z0=1, n0=1, keep=1, keep_coef=1)
     assert n_keep == n_plain + 2 * B * 32 * H * W + B * H * W + 2 * STEPS and ws.numel() >= n_keep
-    assert L.load().ldm_ddim_workspace_floats_keep(ctypes.byref(shape), ctypes.byref(w), -1, 0, 0, 0) < 0
+    assert size(nsteps=-1, z0=1, n0=1, keep=1, keep_coef=1) < 0
     x = xin.to(cuda).clone()
     d = [t.to(cuda) for t in tgt]
     tt, fd, c8, t_table = coef_tables(ctx, cuda, "dpmpp2m", B)
@@ -414,21 +417,22 @@ def test_c_abi_errors(ctx, cuda):
     kops = [z0.to(cuda), n0.to(cuda), mask(B, H, W).to(cuda), fd.keep_coefs(tt).to(cuda)]
     x0l = torch.empty((STEPS,) + tuple(xin.shape), device=cuda)
 
-    def call(name, kp, coef, mid, wsp):
-        L.call(name, ctypes.byref(shape), ctypes.byref(w), x.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), None, None, 0, 0,
-               None, None, None, None, None, *kp, t_table.data_ptr(), coef.data_ptr(), STEPS, *mid, None, 0, wsp,
-               ops.stream_handle())
+    def call(solver, kp, coef, wsp):
+        a = L.SampleArgs(solver=L.SOLVER[solver], nsteps=STEPS, eta=0.0, x=x.data_ptr(), s5=d[0].data_ptr(),
+                         s6=d[1].data_ptr(), z0=kp[0], n0=kp[1], keep=kp[2], keep_coef=kp[3], t_table=t_table.data_ptr(),
+                         coef_table=coef.data_ptr(), x0_logs=x0l.data_ptr(), workspace=wsp, stream=ops.stream_handle())
+        L.call("ldm_sample", ctypes.byref(shape), ctypes.byref(w), ctypes.byref(a))
 
-    forms = (("ldm_ddim_sample_keep", c4, (0.0, x0l.data_ptr())), ("ldm_msolver_sample_keep", c8, (x0l.data_ptr(),)))
-    for name, coef, mid in forms:
+    forms = (("ddim", c4), ("msolver", c8))
+    for name, coef in forms:
         for missing in range(4):
             kp = [None if j == missing else t.data_ptr() for j, t in enumerate(kops)]
             with pytest.raises(L.LDMError, match="keep"):
-                call(name, kp, coef, mid, ws.data_ptr())
+                call(name, kp, coef, ws.data_ptr())
     with pytest.raises(L.LDMError):
         L.call("ldm_keep_blend", x.data_ptr(), None, kops[1].data_ptr(), kops[2].data_ptr(), kops[3].data_ptr(), B, 32, H * W,
                ops.stream_handle())
-    # a workspace sized by the plain function, as an allocation of its own (the entries ask the runtime for the extent
+    # a workspace sized for the plain loop, as an allocation of its own (the entry asks the runtime for the extent
     # of the allocation that holds the pointer; torch's caching allocator would hand out part of a larger one)
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipMalloc.argtypes, hip.hipMalloc.restype = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t], ctypes.c_int
@@ -436,21 +440,21 @@ def test_c_abi_errors(ctx, cuda):
     short = ctypes.c_void_p()
     assert hip.hipMalloc(ctypes.byref(short), n_plain * 4) == 0
     try:
-        for name, coef, mid in forms:
+        for name, coef in forms:
             with pytest.raises(L.LDMError, match="workspace"):
-                call(name, [t.data_ptr() for t in kops], coef, mid, short.value)
+                call(name, [t.data_ptr() for t in kops], coef, short.value)
     finally:
         torch.cuda.synchronize()
         assert hip.hipFree(short) == 0
     torch.cuda.synchronize()
     assert torch.equal(x.cpu(), xin)          # nothing ran
-    # with a NULL keep the entry is the plain one; the good call works afterwards
-    call("ldm_ddim_sample_keep", [None] * 4, c4, (0.0, x0l.data_ptr()), ws.data_ptr())
+    # with a NULL keep the loop is the plain one; the good call works afterwards
+    call("ddim", [None] * 4, c4, ws.data_ptr())
     torch.cuda.synchronize()
     p, _, _ = run(ctx, cuda, eng, "ddim", 0.0, xin, tgt)
     assert torch.equal(x, p)
     x.copy_(xin)
-    call("ldm_ddim_sample_keep", [t.data_ptr() for t in kops], c4, (0.0, x0l.data_ptr()), ws.data_ptr())
+    call("ddim", [t.data_ptr() for t in kops], c4, ws.data_ptr())
     torch.cuda.synchronize()
     k, _, _ = run(ctx, cuda, eng, "ddim", 0.0, xin, tgt, keep=(z0, n0, mask(B, H, W)))
     assert torch.equal(x, k) and not torch.equal(x, p)

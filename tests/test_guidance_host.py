@@ -78,12 +78,13 @@ def test_tile_embedding_shapes(ldm):
 
 def test_signature_table_has_the_new_entries():
     from ldm_amd import _lib
-    for n in ("ldm_ddim_sample_guided", "ldm_msolver_sample_guided", "ldm_ddim_workspace_floats_guided", "ldm_guide_eps"):
+    for n in ("ldm_sample", "ldm_sample_workspace_floats", "ldm_guide_eps"):
         assert n in _lib.SIGNATURES
-    # two base maps, two base biases and the scale on top of the *_mix entries
-    assert len(_lib.SIGNATURES["ldm_ddim_sample_guided"][1]) == len(_lib.SIGNATURES["ldm_ddim_sample_mix"][1]) + 5
-    assert len(_lib.SIGNATURES["ldm_msolver_sample_guided"][1]) == len(_lib.SIGNATURES["ldm_msolver_sample_mix"][1]) + 5
-    assert _lib.SIGNATURES["ldm_ddim_workspace_floats_guided"] == _lib.SIGNATURES["ldm_ddim_workspace_floats_mix"]
+    # two base maps, two base biases and the scale beside the mix fields; the regional keep's four operands
+    fields = [f[0] for f in _lib.SampleArgs._fields_]
+    for f in ("S5", "S6", "key_bias5", "key_bias6", "s5_base", "s6_base", "key_bias5_base", "key_bias6_base",
+              "guide_scale", "z0", "n0", "keep", "keep_coef"):
+        assert fields.count(f) == 1
     assert len(_lib.SIGNATURES["ldm_guide_eps"][1]) == 7
 
 

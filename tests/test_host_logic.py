@@ -103,8 +103,8 @@ def test_conv_plans_and_layer_descs():
         assert p.kind in (1, 2) and p.packed_floats > 0
     assert outs[0] == (64, 16, 64) and outs[4] == (512, 2, 8) and outs[5] == (256, 4, 16) and outs[8] == (32, 16, 64)
     assert L.load().ldm_unet_workspace_floats(ctypes.byref(shape), None) > 0
-    assert L.load().ldm_ddim_workspace_floats(ctypes.byref(shape), None, 49) > L.load().ldm_unet_workspace_floats(
-        ctypes.byref(shape), None)
+    assert L.load().ldm_sample_workspace_floats(ctypes.byref(shape), None, ctypes.byref(L.SampleArgs(nsteps=49))) > \
+        L.load().ldm_unet_workspace_floats(ctypes.byref(shape), None)
     # plans with cross-block K splits need counter + partial space on top
     w = L.UNetWeights()
     L.call("ldm_unet_make_plans", ctypes.byref(shape), ctypes.byref(w))
@@ -114,6 +114,34 @@ def test_conv_plans_and_layer_descs():
     assert w.conv_plan[4].ws_floats == 4 * 512 * 128 + (1 << 16)
     assert L.load().ldm_unet_workspace_floats(ctypes.byref(shape), ctypes.byref(w)) >= \
         L.load().ldm_unet_workspace_floats(ctypes.byref(shape), None) + w.conv_plan[4].ws_floats
+
+
+def test_sample_workspace_sizes():
+    """ldm_sample_workspace_floats without bound plans (no device work): the key counts' 0 = own equivalence, the keep
+    region's size (unet.hip keep_region_floats) on top of either carve, the guided carve at twice the batch."""
+    from ldm_amd import _lib as L
+    B, C, H, W, n = 2, 32, 8, 16, 3
+    shape = L.UNetShape(B, C, H, W, 64)
+    dense = B * C * H * W
+
+    def size(shape=shape, guided=False, keep=False, **kw):
+        a = L.SampleArgs(nsteps=n)
+        for f, v in kw.items():
+            setattr(a, f, v)
+        if guided:
+            a.s5_base = a.s6_base = a.guide_scale = 1     # only read for being set
+        if keep:
+            a.z0 = a.n0 = a.keep = a.keep_coef = 1
+        return int(L.load().ldm_sample_workspace_floats(ctypes.byref(shape) if shape else None, None, ctypes.byref(a)))
+
+    plain = size()
+    assert plain > 0 and plain == size(S5=8, S6=2)            # the maps' own H*W/16, H*W/64
+    assert size(S5=16, S6=4) > plain
+    assert size(guided=True) == size(guided=True, S5=8, S6=2)
+    assert size(keep=True) - plain == 2 * dense + B * H * W + 2 * n
+    assert size(guided=True, keep=True) - size(guided=True) == 3 * dense + B * H * W + n * (2 + B)
+    assert size(guided=True) > 2 * plain
+    assert size(nsteps=-1) < 0 and size(S5=-1) < 0 and size(shape=None) < 0
 
 
 def test_split_k_plan_validation():

@@ -125,7 +125,8 @@ def test_cli_parsing():
 
 def test_signature_table_has_the_new_entries():
     from ldm_amd import _lib
-    for n in ("ldm_attention_folded_keys", "ldm_attention_fold_keys_bias", "ldm_ddim_sample_mix",
-              "ldm_msolver_sample_mix", "ldm_ddim_workspace_floats_mix"):
+    for n in ("ldm_attention_folded_keys", "ldm_attention_fold_keys_bias", "ldm_sample", "ldm_sample_workspace_floats"):
         assert n in _lib.SIGNATURES
-    np.testing.assert_equal(len(_lib.SIGNATURES["ldm_ddim_sample_mix"][1]), len(_lib.SIGNATURES["ldm_ddim_sample"][1]) + 4)
+    fields = [f[0] for f in _lib.SampleArgs._fields_]
+    for f in ("S5", "S6", "key_bias5", "key_bias6"):    # the four mix fields
+        assert fields.count(f) == 1

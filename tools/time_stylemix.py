@@ -1,6 +1,6 @@
 """Times what several style references cost the reverse loop: the captured 49-iteration loop
 (linspace(99, 0, 50): the flagship's) at B = 8 on the 16 x 64 latent, fp32 and fp16 operands, for R = 1, 2, 4
-references.  R = 1 is the plain path (ldm_ddim_sample); R > 1 stacks random style maps with equal weights.
+references.  R = 1 is the plain path (ldm_sample without a mix); R > 1 stacks random style maps with equal weights.
 
 Per configuration: one GraphedDDIM, 3 warm-up replays, then the median and the min..max of 15 replays between stream
 events, divided by the iteration count.  The loop's pre-loop work (time MLP, K/V projections, key fold) is inside.
