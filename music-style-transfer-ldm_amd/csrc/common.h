@@ -242,7 +242,8 @@ bool bneck_fold_supported(int B, int H, int W);
 int bneck_fold_values(const float* wf, const float* kv, float* u, int B, hipStream_t st);
 int bneck_pv(const float* u, const float* p, const float* pb, float* y, int B, int dtype, hipStream_t st);
 
-// uconv.hip: the step kernels of the reverse loop (NHWC activations, see ldm_capi.h)
+// uconv.hip: the step kernels of the reverse loop (NHWC activations, see ldm_capi.h); the kernel and its launchers are
+// uconv_kernel.h's, shared with dec1's guided and regional-keep dispatchers (uconv_guide.hip, uconv_keep.hip)
 struct StepConv {
     const float* x;
     const float* w;
