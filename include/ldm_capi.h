@@ -437,6 +437,30 @@ int64_t ldm_sample_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weig
  * carved out of a larger pool is only known to end inside the pool, and the check is skipped under stream capture
  * (run the loop eagerly once before capturing it). */
 int ldm_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a);
+/* ldm_sample in two phases, for callers that run many loops against one style (the windows of a recording, a sampler
+ * service, a replayed graph).  Both take ldm_sample's arguments and make its checks.
+ * ldm_sample_prepare launches what reads only the style maps (target and base), the key biases, t_table and the
+ * weights: the time MLP over the whole t_table, the guided loop's doubled operands, the style maps' K/V projections,
+ * both key folds and, where it applies, the bottleneck's value fold.  It reads neither x, the logs, coef_table,
+ * guide_scale nor the keep operands, and leaves its results in regions of the workspace that no launch of the run
+ * phase writes.
+ * ldm_sample_run launches the rest (the state's layout in and out, the keep region's fill, the loop) on a workspace
+ * that an ldm_sample_prepare with the same s, w and a — the same map, bias and table contents, key counts, nsteps and
+ * weights — has filled since those last changed; any number of runs may follow one prepare, with other x, logs,
+ * coef_table, eta, solver, guide_scale and keep operands.  A run on a workspace prepared for other contents computes
+ * with those: nothing detects it.
+ * ldm_sample is ldm_sample_prepare then ldm_sample_run: the same launches in the same order, bitwise the same result.
+ * All three make one set of argument checks, so that a struct one entry takes the others take too: ldm_sample_prepare
+ * also wants x and coef_table (and x0_logs for the multistep solver) non-NULL although it reads none of them; a caller
+ * that prepares before it has a state passes the buffers it will run with. */
+int ldm_sample_prepare(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a);
+int ldm_sample_run(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a);
+/* The parts of the workspace that must be zero before a launch (they hold split-K tile counters, which every launch
+ * leaves zero again): ranges[0..3] = {offset, length, offset, length} in floats, a length may be 0.  Every other
+ * float of the workspace is written by ldm_sample_prepare or ldm_sample_run before it is read.  Reads what
+ * ldm_sample_workspace_floats reads. */
+int ldm_sample_workspace_zeroed(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a,
+                                int64_t* ranges);
 /* The guidance and the keep arithmetic on whole tensors.  ldm_guide_eps: out[i] = e_b[i] + scale[i / per_sample] *
  * (e_t[i] - e_b[i]) for B * per_sample elements (out may alias e_t or e_b).  ldm_keep_blend: in place on x (NCHW),
  * with one row coef = {a, b}. */

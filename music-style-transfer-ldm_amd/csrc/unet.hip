@@ -129,6 +129,13 @@ static bool use_bneck_fold(const ldm_unet_shape& s, const ldm_unet_weights* w) {
 
 // S5 / S6: key counts of CA2 / CA1 (style mixing: several references stacked along the keys); 0 = the map's own
 // token count, which is every caller but a style mix.  Only the K/V projections and the folded keys scale.
+// Invariant of the reverse loop's two phases (sample_prepare / sample_run): every region is a range of its own (take()
+// never hands out overlapping ranges), and the regions the prepare phase fills (kv2, kv1, kf2, bf2, kf1, bf1, ubn,
+// s5cat, s6cat, kb5cat, kb6cat, and the time embeddings behind the carve) are written by no launch of the run phase,
+// which writes z1 .. eps, q*, a*, c*, xs, p1, eb, the keep region behind the time embeddings and the two scratch
+// regions.  Those two, convws and uks, are shared by both phases' launches (the K/V projections' split-K partials, the
+// loop's) but carry nothing from one launch to the next beyond counters that are zero between launches.  A region
+// added for prepared data must keep to this: a range of its own that the loop does not write.
 static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float* base, int64_t S5 = 0, int64_t S6 = 0,
                     bool guided = false) {
     const int64_t B = s.B, nf = s.nf, HW = (int64_t)s.H * s.W;
@@ -522,28 +529,64 @@ static int concat_halves(const float* a, const float* b, float* out, int64_t row
     return 0;
 }
 
-static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, float* x, const float* s5, const float* s6,
-                       const int64_t* t_table, const float* coef_table, int32_t nsteps, float eta, float* x0_logs,
-                       float* eps_logs, int64_t log_step_stride, float* workspace, void* stream, bool msolver,
-                       int32_t S5 = 0, int32_t S6 = 0, const float* key_bias5 = nullptr,
-                       const float* key_bias6 = nullptr, const Guide* g = nullptr, const Keep* kp = nullptr) {
-    ldm_unet_shape sh = *sc;   // the shape the body runs at
-    if (g) sh.B = 2 * sc->B;
-    const ldm_unet_shape* s = &sh;
+// What both phases of the loop derive from one set of arguments: the shape the body runs at, the key counts, the
+// workspace's regions and which forms apply.  loop_plan makes the checks that do not depend on the phase, so that
+// the prepare and the run refuse the same arguments.
+struct LoopPlan {
+    ldm_unet_shape sh;    // the shape the body runs at (guided: twice the caller's batch)
+    int S5, S6;           // key counts of CA2 / CA1
+    bool kb5, kb6;        // a key bias reaches the folded keys (guided: the target's or the base's)
+    bool bfold;           // the bottleneck runs on CA1's folded values
+    UNetWs ws;
+    float* temb_all;      // [nsteps*B, 128] behind the carve (ldm_sample_workspace_floats)
+    int64_t dense;        // one step of the logs: the caller's batch
+};
+static int loop_plan(const ldm_unet_shape* sc, const ldm_unet_weights* w, const ldm_sample_args& a, const Guide* g,
+                     LoopPlan& lp) {
+    lp.sh = *sc;
+    if (g) lp.sh.B = 2 * sc->B;
+    const ldm_unet_shape* s = &lp.sh;
     const int L2 = s->H * s->W / 16, L1 = s->H * s->W / 64;
-    if (S5 <= 0) S5 = L2;
-    if (S6 <= 0) S6 = L1;
-    const bool gbias = g && (key_bias5 || key_bias6 || g->key_bias5_base || g->key_bias6_base);
-    const bool mix = S5 != L2 || S6 != L1 || key_bias5 || key_bias6 || gbias;
+    lp.S5 = a.S5 <= 0 ? L2 : a.S5;
+    lp.S6 = a.S6 <= 0 ? L1 : a.S6;
+    lp.kb5 = a.key_bias5 || (g && g->key_bias5_base);
+    lp.kb6 = a.key_bias6 || (g && g->key_bias6_base);
+    const bool mix = lp.S5 != L2 || lp.S6 != L1 || lp.kb5 || lp.kb6;
     LDM_REQUIRE(!mix || w->use_fold, "style mix: the reverse loop attends over several references only with the "
                                      "folded cross-attentions (use_fold)");
-    UNetWs ws = carve(*s, w, workspace, S5, S6, g != nullptr);
-    float* temb_all = workspace + ws.total;   // [nsteps*B, 128] (ldm_sample_workspace_floats)
-    const int64_t dense = (int64_t)sc->B * s->C * s->H * s->W;   // one step of the logs: the caller's batch
-    LDM_REQUIRE(log_step_stride == 0 || log_step_stride >= dense, "ddim_sample: log stride smaller than a step");
-    const int64_t n = log_step_stride ? log_step_stride : dense;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t cw = msolver ? 8 : 4;   // floats per coefficient row
+    lp.ws = carve(*s, w, a.workspace, lp.S5, lp.S6, g != nullptr);
+    lp.temb_all = a.workspace + lp.ws.total;
+    lp.dense = (int64_t)sc->B * s->C * s->H * s->W;
+    LDM_REQUIRE(a.log_step_stride == 0 || a.log_step_stride >= lp.dense, "ddim_sample: log stride smaller than a step");
+    lp.bfold = false;
+    if (w->use_fold) {
+        LDM_REQUIRE(w->ca_wq_raw[0] && w->ca_wq_raw[1] && w->fold_w[0] && w->fold_w[1] && w->fold_pb[0] && w->fold_pb[1],
+                    "ddim_sample: use_fold needs the folded weights");
+        if (w->use_step) {
+            LDM_REQUIRE(s->C == 32 && s->nf == 64, "ddim_sample: the step kernels are built for latent 32 / 64 filters");
+            for (int l = 0; l < 9; ++l) LDM_REQUIRE(w->step_w[l], "ddim_sample: use_step needs the step weights");
+            LDM_REQUIRE(w->step_pb[0] && w->step_pb[1], "ddim_sample: use_step needs the folded biases");
+            LDM_REQUIRE(w->step_dtype >= LDM_DT_F32 && w->step_dtype <= LDM_DT_BF16, "ddim_sample: step_dtype");
+            // the bottleneck's value fold is built for CA1's own 16 keys without a bias: a mix leaves it
+            lp.bfold = use_bneck_fold(*s, w) && lp.S6 == L1 && !lp.kb6;
+        }
+    }
+    return 0;
+}
+
+// The prepare phase: everything that reads only the style maps, the key biases, the t table and the weights, never
+// the sampler state, the logs, the coefficient table or the keep operands.  It fills temb_all, the *cat buffers,
+// kv2 / kv1, kf* / bf* and ubn, which the run phase only reads (the invariant stated on carve).
+static int sample_prepare(const ldm_unet_shape* sc, const ldm_unet_weights* w, const ldm_sample_args& a, const Guide* g,
+                          const LoopPlan& lp) {
+    const ldm_unet_shape* s = &lp.sh;
+    const UNetWs& ws = lp.ws;
+    const int L2 = s->H * s->W / 16, L1 = s->H * s->W / 64;
+    const int32_t nsteps = a.nsteps, S5 = lp.S5, S6 = lp.S6;
+    const int64_t* t_table = a.t_table;
+    const float *s5 = a.s5, *s6 = a.s6, *key_bias5 = a.key_bias5, *key_bias6 = a.key_bias6;
+    float* temb_all = lp.temb_all;
+    hipStream_t st = (hipStream_t)a.stream;
     // The time MLP depends only on t: all nsteps*B embeddings in one launch before the loop (the same
     // evaluations the reference makes one step at a time, model.py:203).
     if (g) {   // both halves share t: the caller's [nsteps, B] rows, each repeated for the base half
@@ -574,6 +617,33 @@ static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, floa
         LDM_TRY(style_kv_tokens(*s, *w, 0, s5, S5, ws.kv2, st));
         LDM_TRY(style_kv_tokens(*s, *w, 1, s6, S6, ws.kv1, st));
     }
+    if (w->use_fold) {
+        LDM_TRY(attention_fold_keys_bias(ws.kv2, w->ca_wq_raw[0], w->ca_bq[0], s->B, 256, 4, S5,
+                                         (float)std::sqrt(1.0 / 64.0), key_bias5, ws.kf2, ws.bf2, st));
+        LDM_TRY(attention_fold_keys_bias(ws.kv1, w->ca_wq_raw[1], w->ca_bq[1], s->B, 512, 4, S6,
+                                         (float)std::sqrt(1.0 / 128.0), key_bias6, ws.kf1, ws.bf1, st));
+        if (lp.bfold) LDM_TRY(bneck_fold_values(w->step_bneck_w, ws.kv1, ws.ubn, s->B, st));
+    }
+    return 0;
+}
+
+// The run phase: the sampler state in and out, the keep region's fill and the loop itself, on a workspace that
+// sample_prepare has filled for the same shape, weights and arguments.  It writes none of the prepared regions.
+static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const ldm_sample_args& a, const Guide* g,
+                      const Keep* kp, const LoopPlan& lp) {
+    const ldm_unet_shape* s = &lp.sh;
+    const UNetWs& ws = lp.ws;
+    const bool msolver = a.solver == LDM_SOLVER_MULTISTEP;
+    const int32_t nsteps = a.nsteps, S5 = lp.S5, S6 = lp.S6;
+    const float eta = msolver ? 0.f : a.eta;
+    float *x = a.x, *x0_logs = a.x0_logs, *eps_logs = a.eps_logs, *temb_all = lp.temb_all;
+    const float* coef_table = a.coef_table;
+    const int64_t* t_table = a.t_table;
+    // the literal loop's unet_forward names the maps, but with kv_ready it reads only their prepared projections
+    const float *s5 = g ? ws.s5cat : a.s5, *s6 = g ? ws.s6cat : a.s6;
+    const int64_t dense = lp.dense, n = a.log_step_stride ? a.log_step_stride : dense;
+    hipStream_t st = (hipStream_t)a.stream;
+    const size_t cw = msolver ? 8 : 4;   // floats per coefficient row
     const int HW = s->H * s->W;
     auto make_fuse = [&](int i, float* xstate) {
         DdimFuse fuse{coef_table + cw * (size_t)i, eta, xstate, x0_logs ? x0_logs + (size_t)i * n : nullptr,
@@ -583,46 +653,32 @@ static int sample_loop(const ldm_unet_shape* sc, const ldm_unet_weights* w, floa
         if (kp) fuse.kz0 = kp->z0, fuse.kn0 = kp->n0, fuse.kw = kp->w, fuse.kcoef = kp->coef + 2 * (size_t)i;
         return fuse;
     };
-    if (w->use_fold) {
-        LDM_REQUIRE(w->ca_wq_raw[0] && w->ca_wq_raw[1] && w->fold_w[0] && w->fold_w[1] && w->fold_pb[0] && w->fold_pb[1],
-                    "ddim_sample: use_fold needs the folded weights");
-        LDM_TRY(attention_fold_keys_bias(ws.kv2, w->ca_wq_raw[0], w->ca_bq[0], s->B, 256, 4, S5,
-                                         (float)std::sqrt(1.0 / 64.0), key_bias5, ws.kf2, ws.bf2, st));
-        LDM_TRY(attention_fold_keys_bias(ws.kv1, w->ca_wq_raw[1], w->ca_bq[1], s->B, 512, 4, S6,
-                                         (float)std::sqrt(1.0 / 128.0), key_bias6, ws.kf1, ws.bf1, st));
-        if (w->use_step) {
-            LDM_REQUIRE(s->C == 32 && s->nf == 64, "ddim_sample: the step kernels are built for latent 32 / 64 filters");
-            for (int l = 0; l < 9; ++l) LDM_REQUIRE(w->step_w[l], "ddim_sample: use_step needs the step weights");
-            LDM_REQUIRE(w->step_pb[0] && w->step_pb[1], "ddim_sample: use_step needs the folded biases");
-            LDM_REQUIRE(w->step_dtype >= LDM_DT_F32 && w->step_dtype <= LDM_DT_BF16, "ddim_sample: step_dtype");
-            // the bottleneck's value fold is built for CA1's own 16 keys without a bias: a mix leaves it
-            const bool bfold = use_bneck_fold(*s, w) && S6 == L1 && !key_bias6;
-            if (bfold) LDM_TRY(bneck_fold_values(w->step_bneck_w, ws.kv1, ws.ubn, s->B, st));
-            LDM_TRY(step_layout(x, ws.xs, sc->B, s->C, HW, true, st));
-            if (g) LDM_TRY(step_layout(x, ws.xs + dense, sc->B, s->C, HW, true, st));
-            float* kreg = temb_all + (size_t)nsteps * (g ? 3 : 1) * sc->B * 128;   // the keep region
-            const int krl = 2 + (g ? sc->B : 0);
-            float* krows = kreg + (g ? 3 : 2) * dense + (int64_t)sc->B * HW;
-            if (kp) {
-                float* kz = kreg + (g ? dense : 0);
-                LDM_TRY(step_layout(kp->z0, kz, sc->B, s->C, HW, true, st));
-                LDM_TRY(step_layout(kp->n0, kz + dense, sc->B, s->C, HW, true, st));
-                LDM_HIP_TRY(hipMemcpyAsync(kz + 2 * dense, kp->w, (size_t)sc->B * HW * 4, hipMemcpyDeviceToDevice, st));
-                const int64_t nr = (int64_t)nsteps * krl;
-                hipLaunchKernelGGL(keep_rows_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, kp->coef,
-                                   g ? g->scale : nullptr, krows, sc->B, nr);
-                LDM_CHECK_LAUNCH("keep_rows_kernel");
-            }
-            for (int i = 0; i < nsteps; ++i) {
-                DdimFuse fuse = make_fuse(i, ws.xs);
-                if (kp) {
-                    fuse.kbase = kreg, fuse.krow = krows + (size_t)i * krl, fuse.kstride = dense;
-                    if (g) fuse.eb = kreg;   // e_b leads the keep region
-                }
-                LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold));
-            }
-            return step_layout(ws.xs, x, sc->B, s->C, HW, false, st);
+    if (w->use_fold && w->use_step) {
+        const bool bfold = lp.bfold;
+        LDM_TRY(step_layout(x, ws.xs, sc->B, s->C, HW, true, st));
+        if (g) LDM_TRY(step_layout(x, ws.xs + dense, sc->B, s->C, HW, true, st));
+        float* kreg = temb_all + (size_t)nsteps * (g ? 3 : 1) * sc->B * 128;   // the keep region
+        const int krl = 2 + (g ? sc->B : 0);
+        float* krows = kreg + (g ? 3 : 2) * dense + (int64_t)sc->B * HW;
+        if (kp) {
+            float* kz = kreg + (g ? dense : 0);
+            LDM_TRY(step_layout(kp->z0, kz, sc->B, s->C, HW, true, st));
+            LDM_TRY(step_layout(kp->n0, kz + dense, sc->B, s->C, HW, true, st));
+            LDM_HIP_TRY(hipMemcpyAsync(kz + 2 * dense, kp->w, (size_t)sc->B * HW * 4, hipMemcpyDeviceToDevice, st));
+            const int64_t nr = (int64_t)nsteps * krl;
+            hipLaunchKernelGGL(keep_rows_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, kp->coef,
+                               g ? g->scale : nullptr, krows, sc->B, nr);
+            LDM_CHECK_LAUNCH("keep_rows_kernel");
         }
+        for (int i = 0; i < nsteps; ++i) {
+            DdimFuse fuse = make_fuse(i, ws.xs);
+            if (kp) {
+                fuse.kbase = kreg, fuse.krow = krows + (size_t)i * krl, fuse.kstride = dense;
+                if (g) fuse.eb = kreg;   // e_b leads the keep region
+            }
+            LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold));
+        }
+        return step_layout(ws.xs, x, sc->B, s->C, HW, false, st);
     }
     // conv.hip's loops keep the state NCHW: in place on x, or when guided on the doubled state in the workspace
     float* xstate = x;
@@ -661,6 +717,23 @@ extern "C" int64_t ldm_sample_workspace_floats(const ldm_unet_shape* s, const ld
     return keep_on(*a) ? n + keep_region_floats(*s, a->nsteps, guided) : n;
 }
 
+// The two scratch regions that hold split-K counters and must be zero before a launch: convws at the carve's start
+// and uks, each with the size carve takes for it.  Everything else in the workspace is written before it is read.
+extern "C" int ldm_sample_workspace_zeroed(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a,
+                                           int64_t* ranges) {
+    LDM_REQUIRE(s && a && ranges && a->S5 >= 0 && a->S6 >= 0 && s->B > 0, "sample_workspace_zeroed: bad argument");
+    const bool guided = guidance_on(*a);
+    ldm_unet_shape sh = *s;
+    if (guided) sh.B = 2 * s->B;
+    float* const base = reinterpret_cast<float*>(uintptr_t(256));   // (only differences of the carved pointers are read)
+    const UNetWs ws = carve(sh, w, base, a->S5, a->S6, guided);
+    ranges[0] = ws.convws - base;
+    ranges[1] = conv_ws_floats(w);
+    ranges[2] = ws.uks - base;
+    ranges[3] = w && w->use_step ? step_ws_floats(sh.B, sh.H, sh.W) : 0;
+    return 0;
+}
+
 // The struct carries no buffer size, and the sizes differ by more than a factor of two between configurations: a
 // buffer sized for another one would be written past its end.  Before anything is launched the extent of the device
 // allocation that holds `workspace` is asked of the runtime and compared with `need` floats.  This is exact for a
@@ -686,7 +759,8 @@ static int workspace_extent_ok(int64_t need, const float* workspace, void* strea
     return 0;
 }
 
-extern "C" int ldm_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a) {
+// The argument checks and the workspace-extent check of all three entries.  *skip: nothing to launch (nsteps == 0).
+static int sample_check(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a, bool* skip) {
     LDM_REQUIRE(s && w && a, "sample: null argument");
     LDM_REQUIRE(a->solver == LDM_SOLVER_DDIM || a->solver == LDM_SOLVER_MULTISTEP, "sample: unknown solver");
     const bool msolver = a->solver == LDM_SOLVER_MULTISTEP;
@@ -704,11 +778,33 @@ extern "C" int ldm_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, co
     }
     LDM_REQUIRE(!keep || (a->z0 && a->n0 && a->keep && a->keep_coef),
                 "sample: z0, n0, keep and keep_coef go together (one is NULL)");
-    if (a->nsteps == 0) return 0;
-    LDM_TRY(workspace_extent_ok(ldm_sample_workspace_floats(s, w, a), a->workspace, a->stream));
+    *skip = a->nsteps == 0;
+    if (*skip) return 0;
+    return workspace_extent_ok(ldm_sample_workspace_floats(s, w, a), a->workspace, a->stream);
+}
+
+enum { PHASE_PREPARE = 1, PHASE_RUN = 2 };
+static int sample_phases(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a, int phases) {
+    bool skip = false;
+    LDM_TRY(sample_check(s, w, a, &skip));
+    if (skip) return 0;
     const Guide g{a->s5_base, a->s6_base, a->key_bias5_base, a->key_bias6_base, a->guide_scale};
     const Keep k{a->z0, a->n0, a->keep, a->keep_coef};
-    return sample_loop(s, w, a->x, a->s5, a->s6, a->t_table, a->coef_table, a->nsteps, msolver ? 0.f : a->eta, a->x0_logs,
-                       a->eps_logs, a->log_step_stride, a->workspace, a->stream, msolver, a->S5, a->S6, a->key_bias5,
-                       a->key_bias6, guided ? &g : nullptr, keep ? &k : nullptr);
+    const Guide* gp = guidance_on(*a) ? &g : nullptr;
+    LoopPlan lp;
+    LDM_TRY(loop_plan(s, w, *a, gp, lp));
+    if (phases & PHASE_PREPARE) LDM_TRY(sample_prepare(s, w, *a, gp, lp));
+    if (phases & PHASE_RUN) LDM_TRY(sample_run(s, w, *a, gp, keep_on(*a) ? &k : nullptr, lp));
+    return 0;
+}
+
+extern "C" int ldm_sample_prepare(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a) {
+    return sample_phases(s, w, a, PHASE_PREPARE);
+}
+extern "C" int ldm_sample_run(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a) {
+    return sample_phases(s, w, a, PHASE_RUN);
+}
+// The prepare followed by the run: the launches ldm_sample always made, in the order it made them.
+extern "C" int ldm_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a) {
+    return sample_phases(s, w, a, PHASE_PREPARE | PHASE_RUN);
 }

@@ -213,6 +213,11 @@ SIGNATURES = {
     "ldm_sample_workspace_floats": (c_int64, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights),
                                               ctypes.POINTER(SampleArgs)]),
     "ldm_sample": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), ctypes.POINTER(SampleArgs)]),
+    "ldm_sample_prepare": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights),
+                                     ctypes.POINTER(SampleArgs)]),
+    "ldm_sample_run": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights), ctypes.POINTER(SampleArgs)]),
+    "ldm_sample_workspace_zeroed": (c_int32, [ctypes.POINTER(UNetShape), ctypes.POINTER(UNetWeights),
+                                              ctypes.POINTER(SampleArgs), ctypes.POINTER(c_int64)]),
     # style mixing (stylemix.hip): key-tiled folded attention with a key bias
     "ldm_attention_folded_keys": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_int32, c_int32,
                                             c_int32, c_vp]),

@@ -6,6 +6,7 @@ Host side only: it owns workspaces (torch allocations) and caches, never compute
 """
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -14,6 +15,17 @@ from . import ops
 from .graphs import capture
 
 byref = ctypes.byref
+
+def prepared_key(operands, weight_version, extra=()):
+    """The host-side key of a prepared reverse-loop workspace (ldm_sample_prepare): (data_ptr, _version, shape) of
+    every tensor the prepare phase reads (None for an absent one), the engine's weight version, and whatever else
+    the prepared state depends on.  Equal keys mean the same storage with no in-place write through torch since;
+    writes through raw pointers do not move a version, so they need an explicit invalidation (GraphedDDIM.invalidate).
+    The key says nothing about a tensor that has been freed (another may live at its address with the same version):
+    it is only compared for tensors that its holder keeps alive (GraphedDDIM's static buffers)."""
+    ops_key = tuple(None if t is None else (t.data_ptr(), t._version, tuple(t.shape)) for t in operands)
+    return ops_key + (weight_version,) + tuple(extra)
+
 
 _CONV_NAMES = ("enc1", "enc2", "enc3", "enc4", "bottleneck", "dec4", "dec3", "dec2", "dec1")
 
@@ -88,6 +100,13 @@ class UNetEngine:
         beyond 512 frames) run the literal loop with the KV-tiled attention (flash.hip)."""
         return shape.H * shape.W <= 1024
 
+    def weight_version(self):
+        """What the bound weights depend on besides the shape: every parameter's (_version, data_ptr), the forced
+        plans and the engine's fold / step / dtype settings.  Host only."""
+        params = self._params()
+        return tuple(p._version for p in params) + tuple(p.data_ptr() for p in params) + \
+            tuple(sorted(ops._PLAN_OVERRIDE.items())) + (self.fold, self.step, self.step_dtype() if self.step else 0)
+
     def weights(self, shape):
         """UNetWeights for this shape, re-packing only the parameters whose _version moved."""
         skey = (shape.B, shape.C, shape.H, shape.W, shape.nf)
@@ -96,8 +115,7 @@ class UNetEngine:
             ops.require_device(p, what="UNet parameter")
             if not p.is_contiguous():
                 raise RuntimeError("UNet parameters must be contiguous")
-        vkey = tuple(p._version for p in params) + tuple(p.data_ptr() for p in params) + \
-            tuple(sorted(ops._PLAN_OVERRIDE.items())) + (self.fold, self.step, self.step_dtype() if self.step else 0)
+        vkey = self.weight_version()
         hit = self._bound.get(skey)
         if hit is not None and hit[0] == vkey:
             return hit[1]
@@ -220,6 +238,11 @@ class UNetEngine:
             ws = torch.zeros(int(n), device=device, dtype=torch.float32)
             self._ws[key] = ws
         return ws
+
+    def release_workspaces(self, slot_prefix):
+        """Drops the workspaces whose slot is a tuple starting with slot_prefix (a GraphedDDIM's private ones)."""
+        for key in [k for k in self._ws if isinstance(k[6], tuple) and k[6][:len(slot_prefix)] == slot_prefix]:
+            del self._ws[key]
 
     def side_streams(self, device, k):
         key = ("streams", str(device))
@@ -411,11 +434,15 @@ class UNetEngine:
                                f"got {tuple(s5.shape)}, {tuple(s6.shape)}")
 
     def _sample_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
-                     key_bias5=None, key_bias6=None, base=None, scale=None, plan_batch=None, keep=None):
+                     key_bias5=None, key_bias6=None, base=None, scale=None, plan_batch=None, keep=None, phase=None):
         """One C loop (ldm_sample) of solver "ddim" / "msolver" on x, with whichever options are given: a mix (stacked
         s5 / s6, key biases), guidance (base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the target's key
         counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights) and the regional
-        keep (keep_operands())."""
+        keep (keep_operands()).
+
+        phase None: the whole loop (ldm_sample).  phase "prepare" / "run": that C entry alone (GraphedDDIM, on
+        workspaces of its own: the engine's shared ones are also written by forward() and by captured graphs' replays,
+        so nothing prepared in them is trusted from one call to the next)."""
         B, C, H, W = x.shape
         shape = self.shape(B, C, H, W)
         n = t_table.shape[0]
@@ -438,7 +465,8 @@ class UNetEngine:
             a.z0, a.n0, a.keep, a.keep_coef = (v.data_ptr() for v in keep)
         a.workspace = self.workspace(shape, x.device, n, slot, keys=(a.S5, a.S6), guided=base is not None,
                                      plan_batch=plan_batch, keep=keep is not None).data_ptr()
-        L.call("ldm_sample", byref(shape), byref(w), byref(a))
+        entry = {None: "ldm_sample", "prepare": "ldm_sample_prepare", "run": "ldm_sample_run"}[phase]
+        L.call(entry, byref(shape), byref(w), byref(a))
 
     def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None, key_bias5=None,
                      key_bias6=None, base=None, guidance_scale=1.0, keep=None):
@@ -593,49 +621,75 @@ class GraphedDDIM:
         self.eta = float(eta)
         # static sub-batch timestep tables, made once outside the captured region
         self.plan = engine.split_plan(self.t_table, x_init.shape[0], split) if split > 1 else None
-        # warm-up (packs weights, allocates workspaces) outside capture
-        self.x.copy_(self.x_init)
-        self._run(plan=self.plan)
-        torch.cuda.synchronize()
-        if not self.plan:
-            self.graphs = [torch.cuda.CUDAGraph()]
-            self.streams = None
-            with capture(self.graphs[0]):
-                self.x.copy_(self.x_init)
-                self._run()
-            return
-        # One graph per sub-batch chain, each replayed on its own stream: a single graph's parallel
-        # branches are executed one after another, separate graphs on separate streams (hardware
-        # queues) run concurrently.
-        self.streams = engine.side_streams(dev, len(self.plan))
-        self.graphs = []
-        per_step = self.x[0].numel() * self.x.shape[0]
-        for k, (lo, hi, t_sub) in enumerate(self.plan):
-            g = torch.cuda.CUDAGraph()
-            with capture(g, stream=self.streams[k]):
-                self.x[lo:hi].copy_(self.x_init[lo:hi])
-                x0l = None if self.x0_logs is None else self.x0_logs[0, lo:hi]
-                epl = None if self.eps_logs is None else self.eps_logs[0, lo:hi]
-                kb5 = None if self.kb5 is None else self.kb5[lo:hi]
-                kb6 = None if self.kb6 is None else self.kb6[lo:hi]
-                gb = None if self.base is None else tuple(None if v is None else v[lo:hi] for v in self.base)
-                gs = None if self.scale is None else self.scale[lo:hi]
-                kc = engine._keep_cut(self.keep, lo, hi)
-                engine._sample_call(solver, self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
-                                    x0l, epl, per_step, k, kb5, kb6, gb, gs, self.x.shape[0] if gb is not None else None,
-                                    kc)
-            self.graphs.append(g)
+        # Workspaces of this object's own (a slot no other caller names): between two replays nothing else writes the
+        # prepared regions, which is what lets a replay skip the prepare graph.
+        self._slot = ("graph", id(self))
+        weakref.finalize(self, engine.release_workspaces, self._slot)
+        self.prepare_launches = 0     # replays that launched the prepare graphs first
+        self._build()
 
-    def _run(self, plan=None):
-        guide = {} if self.base is None else {"base": self.base, "guidance_scale": self.scale}
-        if self.keep is not None:
-            guide["keep"] = self.keep
-        if self.solver == "msolver":
-            self.engine.msolver_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.x0_logs, self.eps_logs,
-                                     plan=plan, key_bias5=self.kb5, key_bias6=self.kb6, **guide)
-        else:
-            self.engine.ddim_loop(self.x, self.s5, self.s6, self.t_table, self.coef, self.eta, self.x0_logs,
-                                  self.eps_logs, plan=plan, key_bias5=self.kb5, key_bias6=self.kb6, **guide)
+    def _chains(self):
+        """(k, lo, hi, t_sub) per sub-batch chain; the whole batch as one chain without a split."""
+        if not self.plan:
+            return [(0, 0, self.x.shape[0], self.t_table)]
+        return [(k, lo, hi, t_sub) for k, (lo, hi, t_sub) in enumerate(self.plan)]
+
+    def _chain_call(self, k, lo, hi, t_sub, phase):
+        """One phase (ldm_sample_prepare / ldm_sample_run) of chain k on its own workspace."""
+        def c(v):
+            return None if v is None else v[lo:hi]
+        split = bool(self.plan)
+        gb = None if self.base is None else tuple(c(v) for v in self.base)
+        x0l = None if self.x0_logs is None else (self.x0_logs[0, lo:hi] if split else self.x0_logs)
+        epl = None if self.eps_logs is None else (self.eps_logs[0, lo:hi] if split else self.eps_logs)
+        per_step = self.x[0].numel() * self.x.shape[0] if split else 0
+        self.engine._sample_call(self.solver, self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
+                                 x0l, epl, per_step, self._slot + (k,), c(self.kb5), c(self.kb6), gb, c(self.scale),
+                                 self.x.shape[0] if (split and gb is not None) else None,
+                                 self.engine._keep_cut(self.keep, lo, hi), phase=phase)
+
+    def _operands(self):
+        """The static tensors the prepare phase reads."""
+        return (self.s5, self.s6, self.kb5, self.kb6) + (self.base if self.base is not None else (None,) * 4) + \
+            (self.t_table,)
+
+    def prepared_key(self, weight_version=None):
+        """prepared_key of the static buffers and the engine's weights as they stand (host only, no device work)."""
+        wv = self.engine.weight_version() if weight_version is None else weight_version
+        return prepared_key(self._operands(), wv)
+
+    def _build(self):
+        """Warm-up, then two captured graphs per chain: the prepare (style and time state) and the loop.  Run again
+        when the engine's weight version moves: a capture holds the addresses of the packed weights."""
+        self.graphs = self.prep_graphs = None
+        self._prepared_key = None
+        self._weight_version = self.engine.weight_version()
+        # warm-up (packs weights, allocates workspaces, runs the entries' eager-only workspace check) outside capture
+        self.x.copy_(self.x_init)
+        for ch in self._chains():
+            self._chain_call(*ch, phase="prepare")
+            self._chain_call(*ch, phase="run")
+        torch.cuda.synchronize()
+        # Without a split one chain on the capture stream.  With one, a pair of graphs per sub-batch chain, each chain
+        # replayed on its own stream: a single graph's parallel branches are executed one after another, separate
+        # graphs on separate streams (hardware queues) run concurrently.
+        self.streams = self.engine.side_streams(self.x.device, len(self.plan)) if self.plan else None
+        self.graphs, self.prep_graphs = [], []
+        for k, lo, hi, t_sub in self._chains():
+            st = None if self.streams is None else self.streams[k]
+            gp, gl = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with capture(gp, stream=st):
+                self._chain_call(k, lo, hi, t_sub, "prepare")
+            with capture(gl, stream=st):
+                self.x[lo:hi].copy_(self.x_init[lo:hi])
+                self._chain_call(k, lo, hi, t_sub, "run")
+            self.prep_graphs.append(gp)
+            self.graphs.append(gl)
+
+    def invalidate(self):
+        """The next replay launches the prepare graphs first.  For callers that write the static style buffers, key
+        biases or t_table through raw pointers, which moves no tensor version (writes through torch are seen)."""
+        self._prepared_key = None
 
     def set_guidance_scale(self, guidance_scale):
         """Writes new strengths (float or [B]) into the static buffer the captured loop reads: the next replay runs
@@ -654,13 +708,32 @@ class GraphedDDIM:
         self.keep[2].copy_(kp[2], non_blocking=False)
 
     def replay(self):
+        """Launches the loop graphs; the prepare graphs first when a static buffer the prepare phase reads (s5, s6,
+        the key biases, the base maps and biases, t_table) or a UNet weight has been written through torch since the
+        last prepare (compared by tensor version on the host), or after invalidate().  x_init, the coefficient
+        table, the guidance scale and the keep operands are read by the loop graphs: no prepare for them."""
+        wv = self.engine.weight_version()
+        if wv != self._weight_version:
+            self._build()
+        key = self.prepared_key(wv)
+        prepare = key != self._prepared_key
+        if prepare:
+            if self.plan:     # the chains read their own contiguous column blocks of t_table
+                for lo, hi, t_sub in self.plan:
+                    t_sub.copy_(self.t_table[:, lo:hi])
+            self._prepared_key = key
+            self.prepare_launches += 1
         if self.streams is None:
+            if prepare:
+                self.prep_graphs[0].replay()
             self.graphs[0].replay()
             return self.x
         main = torch.cuda.current_stream()
-        for st, g in zip(self.streams, self.graphs):
+        for st, gp, g in zip(self.streams, self.prep_graphs, self.graphs):
             st.wait_stream(main)
             with torch.cuda.stream(st):
+                if prepare:
+                    gp.replay()
                 g.replay()
         for st in self.streams:
             main.wait_stream(st)
