@@ -215,6 +215,17 @@ int ldm_attention_folded_keys(const float* z, const float* kv, const float* kf, 
 int ldm_attention_fold_keys_bias(const float* kv, const float* wq, const float* bq, int32_t B, int32_t E,
                                  int32_t heads, int32_t S, float scale, const float* key_bias, float* kf, float* bf,
                                  void* stream);
+/* Style map: ldm_attention_folded_keys with a reference bias on top of the key bias.  The S keys are R references of
+ * S / R keys each (S % R == 0; key s belongs to reference s / (S / R)), and ref_bias [Bm,L,R] (fp32, finite or -inf,
+ * never NaN or +inf) is the log-weight of each reference at each QUERY position:
+ *   out(q_l) = sum_s exp(q_l.k_s + bias_s + ref_bias[b][l][ref(s)]) v_s / (the same sum without v_s).
+ * The softmax lane of (row l, key s) forms xb = (bf[s] (+ key_bias[s])) + ref_bias[b][l][ref(s)], then x = (score) + xb,
+ * in that association, so a ref_bias that is constant over l gives bitwise what the same values give as a key bias.
+ * Samples b >= Bm (0 <= Bm <= B) take no reference bias.  A row whose references are all -inf yields exactly 0.
+ * ref_bias NULL is ldm_attention_folded_keys itself, bitwise.  Same instances (E 256 / 512, 4 heads), any L >= 1. */
+int ldm_attention_folded_keys_map(const float* z, const float* kv, const float* kf, const float* bf,
+                                  const float* key_bias, const float* ref_bias, int32_t R, int32_t Bm, float* out,
+                                  int32_t B, int32_t E, int32_t heads, int32_t L, int32_t S, void* stream);
 /* The folded attention's probabilities only: p [B,heads,L,S] = softmax(z^T kf_h + bf_h) (CA1's instance: E 512,
  * 4 heads, L, S <= 16).  The reverse loop's bottleneck then contracts them with its folded values (below). */
 int ldm_attention_folded_probs(const float* z, const float* kf, const float* bf, float* p, int32_t B, int32_t E,
@@ -389,8 +400,18 @@ typedef struct ldm_sample_args {
      * into bf once per loop, and each step's two attentions stream the keys.  Other key counts or a bias need
      * use_fold (an error otherwise); with S6 != H*W/64 or a key_bias6 the bottleneck runs without its value fold. */
     int32_t S5, S6;
+    /* Style map (refs 0 and both pointers NULL = none; the two pointers go together, one alone is an error): the
+     * log-weight of each of the `refs` stacked references at every query position of the two cross-attentions,
+     * ref_bias5 [B, H*W/16, refs] for CA2 and ref_bias6 [B, H*W/64, refs] for CA1 (fp32, finite or -inf; tokens
+     * row-major as the UNet flattens its maps), as in ldm_attention_folded_keys_map.  S5 and S6 must be refs times the
+     * maps' own counts (refs = 1: the maps' own, given as such or as 0).  Needs use_fold.  The biases add to the key
+     * biases; with guidance they apply to the target half only (the base half runs unbiased); the bottleneck runs
+     * without its value fold.  They are the caller's buffers, read by every step's two attentions in the run phase:
+     * ldm_sample_prepare does not read them, and the workspace size does not depend on them. */
+    int32_t refs;
     float* x;                 /* [B,C,H,W], in place */
     const float *s5, *s6, *key_bias5, *key_bias6;
+    const float *ref_bias5, *ref_bias6;
     /* Style guidance (all five NULL = none; s5_base, s6_base and guide_scale go together, the biases are optional):
      * every step evaluates the denoiser under the target maps (s5 / s6) and the base maps on the same x and t and
      * steps on
@@ -447,7 +468,9 @@ int ldm_sample(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sam
  * ldm_sample_run launches the rest (the state's layout in and out, the keep region's fill, the loop) on a workspace
  * that an ldm_sample_prepare with the same s, w and a — the same map, bias and table contents, key counts, nsteps and
  * weights — has filled since those last changed; any number of runs may follow one prepare, with other x, logs,
- * coef_table, eta, solver, guide_scale and keep operands.  A run on a workspace prepared for other contents computes
+ * coef_table, eta, solver, guide_scale and keep operands, and with other reference biases (ref_bias5 / ref_bias6: the
+ * prepare reads only whether they are set, never their contents, so one prepare serves every window of a recording
+ * whatever its style map).  A run on a workspace prepared for other contents computes
  * with those: nothing detects it.
  * ldm_sample is ldm_sample_prepare then ldm_sample_run: the same launches in the same order, bitwise the same result.
  * All three make one set of argument checks, so that a struct one entry takes the others take too: ldm_sample_prepare

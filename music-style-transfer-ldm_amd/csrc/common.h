@@ -237,6 +237,10 @@ int attention_folded_keys(const float* z, const float* kv, const float* kf, cons
                           float* out, int32_t B, int32_t E, int32_t heads, int32_t L, int32_t S, hipStream_t st);
 int attention_fold_keys_bias(const float* kv, const float* wq, const float* bq, int32_t B, int32_t E, int32_t heads,
                              int32_t S, float scale, const float* key_bias, float* kf, float* bf, hipStream_t st);
+// the style map: attention_folded_keys with a per-(query position, reference) bias ref_bias [Bm,L,R] (NULL: none)
+int attention_folded_keys_map(const float* z, const float* kv, const float* kf, const float* bf, const float* key_bias,
+                              const float* ref_bias, int32_t R, int32_t Bm, float* out, int32_t B, int32_t E, int32_t heads,
+                              int32_t L, int32_t S, hipStream_t st);
 // bfold.hip: the reverse loop's bottleneck with CA1's values folded into its weights (U, once per loop)
 bool bneck_fold_supported(int B, int H, int W);
 int bneck_fold_values(const float* wf, const float* kv, float* u, int B, hipStream_t st);

@@ -14,7 +14,8 @@
 //      loaded to registers here too, and written to LDS after the barrier (the previous tile's P V still reads Vs).
 //   B  softmax: one lane per key, rows over the waves: sums the slabs in wave order, adds bf (+ key_bias), updates
 //      m and l (registers: a row always lands on the same lanes), writes p = exp(x - m) to Pn and the row's
-//      rescale factor to Al.
+//      rescale factor to Al.  The reference-bias form (RB, the style map) adds ref_bias[b][row][ref(s)] to the
+//      lane's bias per row: loaded in A with the other operands, so B waits on nothing new.
 //   C  O = O * alpha + V P^T on fp32 MFMA 16x16x4: channel tiles round-robin over the waves, accumulators in
 //      registers across all key tiles; the division by l happens once, at the store.
 // A key tile (or the leading tiles) may be entirely -inf: m stays -inf, and exp's argument is taken against 0
@@ -38,13 +39,18 @@
 
 namespace ldm {
 
-template <int D, int EQ, int ST, int NW>
+// RB: the reference-bias form.  ref_bias [Bm, L, R] (fp32, finite or -inf) is the log-weight of reference
+// ref(s) = s / (S / R) at query position l; samples b >= Bm take none (the guided loop's base half).  Without RB the
+// three trailing arguments are unused and the code below is what it was.
+template <int D, int EQ, int ST, int NW, bool RB>
 __global__ __launch_bounds__(64 * NW) void attention_folded_tiled_kernel(const float* __restrict__ z,
                                                                          const float* __restrict__ kv,
                                                                          const float* __restrict__ kf,
                                                                          const float* __restrict__ bf,
                                                                          const float* __restrict__ key_bias,
-                                                                         float* __restrict__ out, int heads, int L, int S) {
+                                                                         float* __restrict__ out, int heads, int L, int S,
+                                                                         const float* __restrict__ ref_bias, int R,
+                                                                         int Bm) {
     constexpr int TILE = 16, NLG = 4, LT = 16;
     constexpr int NSTEP = EQ / NW / NLG;          // MFMA steps of one wave's slice of the score contraction
     constexpr int NTS = ST / TILE;                // score tiles per key tile
@@ -97,6 +103,18 @@ __global__ __launch_bounds__(64 * NW) void attention_folded_tiled_kernel(const f
     floatx4 acc[NTO];
 #pragma unroll
     for (int i = 0; i < NTO; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+    // reference bias: each softmax pass' row of ref_bias (rows past L read row L - 1: never stored); the whole block
+    // is one sample, so whether it takes a bias is uniform
+    [[maybe_unused]] const float* rbrow[NPASS];
+    [[maybe_unused]] const bool rbon = RB && b < Bm;
+    [[maybe_unused]] const int SR = RB ? S / R : 1;   // keys per reference
+    if constexpr (RB) {
+#pragma unroll
+        for (int p = 0; p < NPASS; ++p) {
+            const int l = l0 + (wave + NW * p) * RPW + sub;
+            rbrow[p] = ref_bias + ((size_t)(rbon ? b : 0) * L + (l < L ? l : L - 1)) * R;
+        }
+    }
 
     for (int sb = 0; sb < S; sb += ST) {
         // ---- A: this tile's folded keys and values, every load in flight before the first MFMA
@@ -127,6 +145,17 @@ __global__ __launch_bounds__(64 * NW) void attention_folded_tiled_kernel(const f
             const int s = sb + s0;
             xb = s < S ? bfb[s] + (kbias ? kbias[s] : 0.f) : -INFINITY;
         }
+        [[maybe_unused]] float rb[NPASS];   // per row: the bias of this lane's key's reference (keys past S read the last)
+        if constexpr (RB) {
+#pragma unroll
+            for (int p = 0; p < NPASS; ++p) rb[p] = 0.f;
+            if (rbon) {
+                const int s = sb + s0;
+                const int ref = (s < S ? s : S - 1) / SR;
+#pragma unroll
+                for (int p = 0; p < NPASS; ++p) rb[p] = rbrow[p][ref];
+            }
+        }
         float* Sw = Sc + wave * LT * LDSC;
 #pragma unroll
         for (int st = 0; st < NTS; ++st) {
@@ -149,7 +178,8 @@ __global__ __launch_bounds__(64 * NW) void attention_folded_tiled_kernel(const f
             float x = Sc[r * LDSC + s0];
 #pragma unroll
             for (int w = 1; w < NW; ++w) x = x + Sc[w * LT * LDSC + r * LDSC + s0];
-            x += xb;
+            if constexpr (RB) x += rbon ? xb + rb[p] : xb;
+            else x += xb;
             float mx = x;
 #pragma unroll
             for (int o = ST / 2; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
@@ -225,12 +255,38 @@ int attention_folded_keys(const float* z, const float* kv, const float* kf, cons
     const int64_t blocks = (int64_t)B * heads * ((L + 15) / 16);
     LDM_REQUIRE(blocks < (int64_t)1 << 31, "attention (folded, keys): too many query tiles");
     if (E == 256)
-        hipLaunchKernelGGL((attention_folded_tiled_kernel<64, 256, 64, 4>), dim3((unsigned)blocks), dim3(256), 0, st, z, kv,
-                           kf, bf, key_bias, out, heads, L, S);
+        hipLaunchKernelGGL((attention_folded_tiled_kernel<64, 256, 64, 4, false>), dim3((unsigned)blocks), dim3(256), 0, st,
+                           z, kv, kf, bf, key_bias, out, heads, L, S, nullptr, 0, 0);
     else
-        hipLaunchKernelGGL((attention_folded_tiled_kernel<128, 512, 32, 8>), dim3((unsigned)blocks), dim3(512), 0, st, z, kv,
-                           kf, bf, key_bias, out, heads, L, S);
+        hipLaunchKernelGGL((attention_folded_tiled_kernel<128, 512, 32, 8, false>), dim3((unsigned)blocks), dim3(512), 0, st,
+                           z, kv, kf, bf, key_bias, out, heads, L, S, nullptr, 0, 0);
     LDM_CHECK_LAUNCH("attention_folded_tiled_kernel");
+    return 0;
+}
+
+// The style map: attention_folded_keys with a per-(query position, reference) bias ref_bias [Bm, L, R] on top of the
+// key bias; key s belongs to reference s / (S / R), samples b >= Bm take none.  ref_bias NULL (or Bm == 0) is
+// attention_folded_keys itself.  Always the streaming kernel: the bias lives in its softmax phase.
+int attention_folded_keys_map(const float* z, const float* kv, const float* kf, const float* bf, const float* key_bias,
+                              const float* ref_bias, int32_t R, int32_t Bm, float* out, int32_t B, int32_t E, int32_t heads,
+                              int32_t L, int32_t S, hipStream_t st) {
+    if (!ref_bias || Bm == 0) return attention_folded_keys(z, kv, kf, bf, key_bias, out, B, E, heads, L, S, st);
+    LDM_REQUIRE(z && kv && kf && bf && out, "attention (folded, map): null argument");
+    LDM_REQUIRE(B > 0 && heads == 4 && L > 0 && S > 0 && (E == 256 || E == 512),
+                "attention (folded, map): instances for E 256 and 512 at 4 heads");
+    LDM_REQUIRE(R >= 1 && S % R == 0, "attention (folded, map): the key count must be a multiple of the reference count");
+    LDM_REQUIRE(Bm > 0 && Bm <= B, "attention (folded, map): the biased sample count must lie in [0, B]");
+    LDM_REQUIRE((((uintptr_t)z | (uintptr_t)kf | (uintptr_t)out) & 15) == 0,
+                "attention (folded, map): z, kf and out must be 16-byte aligned");
+    const int64_t blocks = (int64_t)B * heads * ((L + 15) / 16);
+    LDM_REQUIRE(blocks < (int64_t)1 << 31, "attention (folded, map): too many query tiles");
+    if (E == 256)
+        hipLaunchKernelGGL((attention_folded_tiled_kernel<64, 256, 64, 4, true>), dim3((unsigned)blocks), dim3(256), 0, st,
+                           z, kv, kf, bf, key_bias, out, heads, L, S, ref_bias, R, Bm);
+    else
+        hipLaunchKernelGGL((attention_folded_tiled_kernel<128, 512, 32, 8, true>), dim3((unsigned)blocks), dim3(512), 0, st,
+                           z, kv, kf, bf, key_bias, out, heads, L, S, ref_bias, R, Bm);
+    LDM_CHECK_LAUNCH("attention_folded_tiled_kernel (map)");
     return 0;
 }
 
@@ -251,6 +307,14 @@ extern "C" int ldm_attention_folded_keys(const float* z, const float* kv, const 
                                          const float* key_bias, float* out, int32_t B, int32_t E, int32_t heads,
                                          int32_t L, int32_t S, void* stream) {
     return ldm::attention_folded_keys(z, kv, kf, bf, key_bias, out, B, E, heads, L, S, (hipStream_t)stream);
+}
+
+extern "C" int ldm_attention_folded_keys_map(const float* z, const float* kv, const float* kf, const float* bf,
+                                             const float* key_bias, const float* ref_bias, int32_t R, int32_t Bm,
+                                             float* out, int32_t B, int32_t E, int32_t heads, int32_t L, int32_t S,
+                                             void* stream) {
+    return ldm::attention_folded_keys_map(z, kv, kf, bf, key_bias, ref_bias, R, Bm, out, B, E, heads, L, S,
+                                          (hipStream_t)stream);
 }
 
 extern "C" int ldm_attention_fold_keys_bias(const float* kv, const float* wq, const float* bq, int32_t B, int32_t E,

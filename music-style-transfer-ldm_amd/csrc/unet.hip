@@ -340,23 +340,38 @@ static int unet_forward(const ldm_unet_shape& s, const ldm_unet_weights& w, cons
     return 0;
 }
 
+// The style map of a loop: per-(query position, reference) biases of CA2 / CA1 ([Bm,L2,R] / [Bm,L1,R], the caller's
+// buffers), read by each step's two attentions (attention_folded_keys_map).  NULL: the launches are the key-bias ones.
+struct RefBias {
+    const float *b5, *b6;
+    int R, Bm;   // references; samples that take the bias (guided: the target half)
+};
+// CA2 (j = 0) / CA1 (j = 1) of a folded step
+static int step_attention(int j, const float* z, const float* kv, const float* kf, const float* bf, float* out, int B, int L,
+                          int S, const RefBias* rb, hipStream_t st) {
+    const int E = j ? 512 : 256;
+    if (!rb) return attention_folded_keys(z, kv, kf, bf, nullptr, out, B, E, 4, L, S, st);
+    return attention_folded_keys_map(z, kv, kf, bf, nullptr, j ? rb->b6 : rb->b5, rb->R, rb->Bm, out, B, E, 4, L, S, st);
+}
+
 // The reverse loop's step with both cross-attentions re-associated (style and weights are fixed for the
 // whole loop): the Q in-projection folds into the keys (ldm_attention_fold_keys, once per loop) and the
 // out-projection into the following conv (ldm_fold_conv_proj, once per weight version).  11 launches per
 // step instead of 15; the same arithmetic up to fp32 re-association.
 static int unet_forward_folded(const ldm_unet_shape& s, const ldm_unet_weights& w, const float* z, const UNetWs& ws,
-                               hipStream_t st, const float* temb, const DdimFuse* fuse, int S5, int S6) {
+                               hipStream_t st, const float* temb, const DdimFuse* fuse, int S5, int S6,
+                               const RefBias* rb) {
     const int HW = s.H * s.W;
     const int L2 = HW / 16, L1 = HW / 64;
     LDM_TRY(conv_call(s, ws.convws, 0, w.conv_plan[0], z, w.conv_w[0], w.conv_b[0], LDM_ACT_RELU, nullptr, nullptr, ws.z1, st));
     LDM_TRY(conv_call(s, ws.convws, 1, w.conv_plan[1], ws.z1, w.conv_w[1], w.conv_b[1], LDM_ACT_RELU, temb, nullptr, ws.z2, st));
     LDM_TRY(conv_call(s, ws.convws, 2, w.conv_plan[2], ws.z2, w.conv_w[2], w.conv_b[2], LDM_ACT_RELU, nullptr, nullptr, ws.z3, st));
     // cross_attention2 then enc4 (model.py:211-212)
-    LDM_TRY(attention_folded_keys(ws.z3, ws.kv2, ws.kf2, ws.bf2, nullptr, ws.a2, s.B, 256, 4, L2, S5, st));
+    LDM_TRY(step_attention(0, ws.z3, ws.kv2, ws.kf2, ws.bf2, ws.a2, s.B, L2, S5, rb, st));
     LDM_TRY(conv_call(s, ws.convws, 3, w.conv_plan[3], ws.a2, w.fold_w[0], nullptr, LDM_ACT_RELU, nullptr, nullptr, ws.z4, st,
                       nullptr, w.fold_pb[0]));
     // cross_attention1 then bottleneck (model.py:214-217)
-    LDM_TRY(attention_folded_keys(ws.z4, ws.kv1, ws.kf1, ws.bf1, nullptr, ws.a1, s.B, 512, 4, L1, S6, st));
+    LDM_TRY(step_attention(1, ws.z4, ws.kv1, ws.kf1, ws.bf1, ws.a1, s.B, L1, S6, rb, st));
     LDM_TRY(conv_call(s, ws.convws, 4, w.conv_plan[4], ws.a1, w.fold_w[1], nullptr, LDM_ACT_RELU, nullptr, nullptr, ws.zb, st,
                       nullptr, w.fold_pb[1]));
     LDM_TRY(conv_call(s, ws.convws, 5, w.conv_plan[5], ws.zb, w.conv_w[5], w.conv_b[5], LDM_ACT_RELU, nullptr, ws.z3, ws.d4, st));
@@ -369,7 +384,7 @@ static int unet_forward_folded(const ldm_unet_shape& s, const ldm_unet_weights& 
 // The same folded step on the step kernels (uconv.hip): x and every activation NHWC, 11 launches, the
 // DDIM update fused into dec1.  z (the sampler state) is ws.xs.
 static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w, const UNetWs& ws, hipStream_t st,
-                             const float* temb, const DdimFuse& fuse, int S5, int S6, bool bfold) {
+                             const float* temb, const DdimFuse& fuse, int S5, int S6, bool bfold, const RefBias* rb) {
     const int HW = s.H * s.W;
     const int L2 = HW / 16, L1 = HW / 64;
     // the nine convs' operands: enc1..enc3, enc4 (after CA2), bottleneck (after CA1), dec4..dec2, dec1 + DDIM
@@ -422,7 +437,7 @@ static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w,
         return 0;
     };
     LDM_TRY(run(0, 2));
-    LDM_TRY(attention_folded_keys(ws.z3, ws.kv2, ws.kf2, ws.bf2, nullptr, ws.a2, s.B, 256, 4, L2, S5, st));
+    LDM_TRY(step_attention(0, ws.z3, ws.kv2, ws.kf2, ws.bf2, ws.a2, s.B, L2, S5, rb, st));
     LDM_TRY(run(3, 3));
     if (bfold) {
         // CA1's probabilities, then the bottleneck on its folded values U (formed before the loop)
@@ -431,7 +446,7 @@ static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w,
         LDM_TRY(bneck_pv(ws.ubn, ws.p1, w.step_pb[1], ws.zb, s.B, w.step_dtype, st));
         return run(5, 8);
     }
-    LDM_TRY(attention_folded_keys(ws.z4, ws.kv1, ws.kf1, ws.bf1, nullptr, ws.a1, s.B, 512, 4, L1, S6, st));
+    LDM_TRY(step_attention(1, ws.z4, ws.kv1, ws.kf1, ws.bf1, ws.a1, s.B, L1, S6, rb, st));
     return run(4, 8);
 }
 
@@ -483,6 +498,9 @@ extern "C" int ldm_unet_forward(const ldm_unet_shape* s, const ldm_unet_weights*
 // sample, the K/V projections and the key fold run over them, the bias goes into the folded keys' bias, and the
 // two attention launches of each step stream the keys (stylemix.hip).  With the maps' own counts and no bias every
 // call below is the one it always was.
+// Style map (ref_bias5 / ref_bias6 with refs): the weight of each stacked reference per query position.  It has a query
+// axis, so it cannot go into bf: each step's two attention launches read it (attention_folded_keys_map), and the
+// prepare phase does not.  Guided, it applies to the target half only (Bm = the caller's batch).
 // Style guidance (g != NULL): every step evaluates the denoiser under the target and under a
 // base style and steps on eps = e_b + scale (e_t - e_b) (guide_eps).  The body runs at twice the caller's batch,
 // samples [0, B) under the target maps and [B, 2B) under the base maps, on a doubled sampler state whose halves
@@ -537,6 +555,8 @@ struct LoopPlan {
     int S5, S6;           // key counts of CA2 / CA1
     bool kb5, kb6;        // a key bias reaches the folded keys (guided: the target's or the base's)
     bool bfold;           // the bottleneck runs on CA1's folded values
+    bool map;             // a style map: each step's two attentions read the reference biases (run phase only)
+    RefBias rb;
     UNetWs ws;
     float* temb_all;      // [nsteps*B, 128] behind the carve (ldm_sample_workspace_floats)
     int64_t dense;        // one step of the logs: the caller's batch
@@ -554,6 +574,14 @@ static int loop_plan(const ldm_unet_shape* sc, const ldm_unet_weights* w, const 
     const bool mix = lp.S5 != L2 || lp.S6 != L1 || lp.kb5 || lp.kb6;
     LDM_REQUIRE(!mix || w->use_fold, "style mix: the reverse loop attends over several references only with the "
                                      "folded cross-attentions (use_fold)");
+    lp.map = a.ref_bias5 != nullptr;
+    lp.rb = RefBias{a.ref_bias5, a.ref_bias6, a.refs, sc->B};
+    if (lp.map) {
+        LDM_REQUIRE(w->use_fold, "style map: the reverse loop takes per-position reference weights only with the "
+                                 "folded cross-attentions (use_fold)");
+        LDM_REQUIRE((int64_t)a.refs * L2 == lp.S5 && (int64_t)a.refs * L1 == lp.S6,
+                    "style map: S5 / S6 must be refs times the maps' own token counts");
+    }
     lp.ws = carve(*s, w, a.workspace, lp.S5, lp.S6, g != nullptr);
     lp.temb_all = a.workspace + lp.ws.total;
     lp.dense = (int64_t)sc->B * s->C * s->H * s->W;
@@ -568,14 +596,15 @@ static int loop_plan(const ldm_unet_shape* sc, const ldm_unet_weights* w, const 
             LDM_REQUIRE(w->step_pb[0] && w->step_pb[1], "ddim_sample: use_step needs the folded biases");
             LDM_REQUIRE(w->step_dtype >= LDM_DT_F32 && w->step_dtype <= LDM_DT_BF16, "ddim_sample: step_dtype");
             // the bottleneck's value fold is built for CA1's own 16 keys without a bias: a mix leaves it
-            lp.bfold = use_bneck_fold(*s, w) && lp.S6 == L1 && !lp.kb6;
+            lp.bfold = use_bneck_fold(*s, w) && lp.S6 == L1 && !lp.kb6 && !lp.map;   // (nor does a style map)
         }
     }
     return 0;
 }
 
 // The prepare phase: everything that reads only the style maps, the key biases, the t table and the weights, never
-// the sampler state, the logs, the coefficient table or the keep operands.  It fills temb_all, the *cat buffers,
+// the sampler state, the logs, the coefficient table, the keep operands or the style map's reference biases (lp.rb is
+// not touched here: any number of runs with other biases may follow).  It fills temb_all, the *cat buffers,
 // kv2 / kv1, kf* / bf* and ubn, which the run phase only reads (the invariant stated on carve).
 static int sample_prepare(const ldm_unet_shape* sc, const ldm_unet_weights* w, const ldm_sample_args& a, const Guide* g,
                           const LoopPlan& lp) {
@@ -645,6 +674,7 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
     hipStream_t st = (hipStream_t)a.stream;
     const size_t cw = msolver ? 8 : 4;   // floats per coefficient row
     const int HW = s->H * s->W;
+    const RefBias* rb = lp.map ? &lp.rb : nullptr;
     auto make_fuse = [&](int i, float* xstate) {
         DdimFuse fuse{coef_table + cw * (size_t)i, eta, xstate, x0_logs ? x0_logs + (size_t)i * n : nullptr,
                       eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
@@ -676,7 +706,7 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
                 fuse.kbase = kreg, fuse.krow = krows + (size_t)i * krl, fuse.kstride = dense;
                 if (g) fuse.eb = kreg;   // e_b leads the keep region
             }
-            LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold));
+            LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold, rb));
         }
         return step_layout(ws.xs, x, sc->B, s->C, HW, false, st);
     }
@@ -692,7 +722,7 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
         // (model.py:442-463) — bitwise the same fp32 op sequence as ldm_ddim_step.
         const DdimFuse fuse = make_fuse(i, xstate);
         if (w->use_fold)
-            LDM_TRY(unet_forward_folded(*s, *w, xstate, ws, st, temb_all + (size_t)i * s->B * 128, &fuse, S5, S6));
+            LDM_TRY(unet_forward_folded(*s, *w, xstate, ws, st, temb_all + (size_t)i * s->B * 128, &fuse, S5, S6, rb));
         else
             LDM_TRY(unet_forward(*s, *w, xstate, t_table + (size_t)i * sc->B, 0, s5, s6, nullptr, ws, st,
                                  temb_all + (size_t)i * s->B * 128, &fuse, /*kv_ready=*/true));
@@ -778,6 +808,10 @@ static int sample_check(const ldm_unet_shape* s, const ldm_unet_weights* w, cons
     }
     LDM_REQUIRE(!keep || (a->z0 && a->n0 && a->keep && a->keep_coef),
                 "sample: z0, n0, keep and keep_coef go together (one is NULL)");
+    LDM_REQUIRE((a->ref_bias5 != nullptr) == (a->ref_bias6 != nullptr),
+                "sample: ref_bias5 and ref_bias6 go together (one is NULL)");
+    LDM_REQUIRE(a->ref_bias5 ? a->refs >= 1 : a->refs == 0,
+                "sample: refs is the reference count of ref_bias5 / ref_bias6 (at least 1 with them, 0 without)");
     *skip = a->nsteps == 0;
     if (*skip) return 0;
     return workspace_extent_ok(ldm_sample_workspace_floats(s, w, a), a->workspace, a->stream);

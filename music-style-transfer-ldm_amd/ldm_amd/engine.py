@@ -324,6 +324,45 @@ class UNetEngine:
         return S5, S6, ptrs[0], ptrs[1]
 
     @staticmethod
+    def map_refs(x, s5, s6):
+        """R of stacked style maps (s5 [B,256,R*H/4,W/4]): the reference count a style map's biases must have."""
+        L2 = (x.shape[2] // 4) * (x.shape[3] // 4)
+        return (s5.shape[2] * s5.shape[3]) // L2 if s5.dim() == 4 and L2 else 0
+
+    @staticmethod
+    def map_layout_check(xshape, R, ref_bias5, ref_bias6):
+        """A style map's biases for a state of xshape and R references, checked on the host without device work: both
+        given, contiguous fp32 ref_bias5 [B,H*W/16,R] / ref_bias6 [B,H*W/64,R] (ValueError), on the GPU (RuntimeError)."""
+        if ref_bias5 is None or ref_bias6 is None:
+            raise ValueError("style map: ref_bias5 and ref_bias6 go together (one is None)")
+        B, C, H, W = xshape
+        if R < 1:
+            raise ValueError("style map: the biases need stacked style maps of R >= 1 references (LDM.encode_styles)")
+        for rb, Lq, name in ((ref_bias5, (H // 4) * (W // 4), "ref_bias5"), (ref_bias6, (H // 8) * (W // 8), "ref_bias6")):
+            if not isinstance(rb, torch.Tensor):
+                raise ValueError(f"style map: {name} must be a tensor")
+            if rb.dtype != torch.float32 or tuple(rb.shape) != (B, Lq, R) or not rb.is_contiguous():
+                raise ValueError(f"style map: {name} must be a contiguous fp32 [{B},{Lq},{R}] tensor (one log-weight per "
+                                 f"sample, query position and reference), got {rb.dtype} {tuple(rb.shape)}")
+        ops.require_device(ref_bias5, ref_bias6, what="style map bias")
+
+    def _map_check(self, x, s5, s6, ref_bias5, ref_bias6):
+        """A style map's operands checked against the loop's (no device work).  Returns (R, S5, S6, pointers)."""
+        if ref_bias5 is None or ref_bias6 is None:
+            raise ValueError("style map: ref_bias5 and ref_bias6 go together (one is None)")
+        S5, S6, _, _ = self._mix_check(x, s5, s6, None, None)    # stacked maps of one R, the folded engine
+        R = self.map_refs(x, s5, s6)
+        self.map_layout_check(tuple(x.shape), R, ref_bias5, ref_bias6)
+        return R, S5, S6, ref_bias5.data_ptr(), ref_bias6.data_ptr()
+
+    @staticmethod
+    def map_values_check(ref_bias5, ref_bias6):
+        """The biases' values (a device reduction and a host read): finite or -inf; NaN and +inf are refused."""
+        for rb, name in ((ref_bias5, "ref_bias5"), (ref_bias6, "ref_bias6")):
+            if bool(torch.isnan(rb).any()) or bool((rb == float("inf")).any()):
+                raise ValueError(f"style map: {name} must be finite or -inf (NaN / +inf given)")
+
+    @staticmethod
     def guidance_scale(scale, B, device=None):
         """The per-sample guidance strengths as a contiguous fp32 [B] tensor (on `device` when given): a Python
         number is broadcast, a tensor must hold B entries.  Finite values only (negative allowed): ValueError
@@ -434,11 +473,13 @@ class UNetEngine:
                                f"got {tuple(s5.shape)}, {tuple(s6.shape)}")
 
     def _sample_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
-                     key_bias5=None, key_bias6=None, base=None, scale=None, plan_batch=None, keep=None, phase=None):
+                     key_bias5=None, key_bias6=None, base=None, scale=None, plan_batch=None, keep=None, phase=None,
+                     ref_bias5=None, ref_bias6=None):
         """One C loop (ldm_sample) of solver "ddim" / "msolver" on x, with whichever options are given: a mix (stacked
         s5 / s6, key biases), guidance (base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the target's key
         counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights) and the regional
-        keep (keep_operands()).
+        keep (keep_operands()).  ref_bias5 / ref_bias6: the style map's biases (ddim_loop); their layout is checked here,
+        their values by the callers (no device work in this function: it runs under capture).
 
         phase None: the whole loop (ldm_sample).  phase "prepare" / "run": that C entry alone (GraphedDDIM, on
         workspaces of its own: the engine's shared ones are also written by forward() and by captured graphs' replays,
@@ -463,26 +504,32 @@ class UNetEngine:
         if keep is not None:
             keep = self.keep_operands(keep, x.shape, n, x.device)
             a.z0, a.n0, a.keep, a.keep_coef = (v.data_ptr() for v in keep)
+        if ref_bias5 is not None or ref_bias6 is not None:
+            a.refs, S5, S6, a.ref_bias5, a.ref_bias6 = self._map_check(x, s5, s6, ref_bias5, ref_bias6)
+            if not a.S5:    # one reference without a key bias: the maps' own counts, stated
+                a.S5, a.S6 = S5, S6
         a.workspace = self.workspace(shape, x.device, n, slot, keys=(a.S5, a.S6), guided=base is not None,
                                      plan_batch=plan_batch, keep=keep is not None).data_ptr()
         entry = {None: "ldm_sample", "prepare": "ldm_sample_prepare", "run": "ldm_sample_run"}[phase]
         L.call(entry, byref(shape), byref(w), byref(a))
 
     def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None, key_bias5=None,
-                     key_bias6=None, base=None, guidance_scale=1.0, keep=None):
+                     key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None, ref_bias6=None):
         """ddim_loop's twin for the multistep solver (DPM-Solver++(2M) or its first-order form): coef_table
         [n,8] from ForwardDiffusion.multistep_coefs (device), no eta.  x0_logs [n,B,C,H,W] is required: step i
-        reads step i-1's slot as its history.  Same sub-batch chains, base=, guidance_scale= and keep= as ddim_loop."""
+        reads step i-1's slot as its history.  Same sub-batch chains, base=, guidance_scale=, keep= and style map
+        (ref_bias5= / ref_bias6=) as ddim_loop."""
         if x0_logs is None:
             raise ValueError("msolver_loop: x0_logs is required (it is the solver's history)")
         if coef_table.dim() != 2 or coef_table.shape[1] != 8 or coef_table.shape[0] != t_table.shape[0]:
             raise ValueError(f"msolver_loop: coef_table must be [n,8] for n = {t_table.shape[0]} steps, "
                              f"got {tuple(coef_table.shape)}")
         return self._loop("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, split, plan, key_bias5,
-                          key_bias6, base, guidance_scale, keep)
+                          key_bias6, base, guidance_scale, keep, ref_bias5, ref_bias6)
 
     def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None,
-                  key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None):
+                  key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None,
+                  ref_bias6=None):
         """In-place reverse loop on x ([B,C,H,W] contiguous fp32).  t_table [n,B] int64, coef [n,4] (device).
 
         Style mixing: s5 / s6 may hold R style references stacked along the map's height (s5 [B,256,R*H/4,W/4],
@@ -502,16 +549,22 @@ class UNetEngine:
         the logs stay the model's own prediction.  Composes with the mix, the guidance and the split (each chain gets
         its slice).  ValueError for a w outside [0, 1] or not finite, and for wrong shapes.
 
+        Style map: ref_bias5 [B,H*W/16,R] / ref_bias6 [B,H*W/64,R] (contiguous fp32 on the device, finite or -inf; both
+        or neither) give the log-weight of each of the R stacked references at every query position of the two
+        cross-attentions (tokens row-major as the UNet flattens its maps; LDM.style_map_bias builds them).  They add
+        to the key biases, apply to the target half only under guidance, and are read by every step's attentions, not
+        folded before the loop.  ValueError for a wrong shape, dtype or device and for NaN / +inf.
+
         split > 1 runs the batch as that many independent sub-batch chains, each on its own stream
         (forked from and joined back into the current stream, so it also works under graph capture).
         The path is per-sample, so the result is the same up to fp32 summation order (a sub-batch
         size may get a conv plan that splits K differently); the chains' launch and memory latencies
         overlap each other's work."""
         return self._loop("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, split, plan, key_bias5,
-                          key_bias6, base, guidance_scale, keep)
+                          key_bias6, base, guidance_scale, keep, ref_bias5, ref_bias6)
 
     def _loop(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, split, plan, key_bias5=None,
-              key_bias6=None, base=None, guidance_scale=1.0, keep=None):
+              key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None, ref_bias6=None):
         """The whole batch in one _sample_call, or one per sub-batch chain with every per-sample operand (the maps, the
         biases, the base, the scales, the keep operands, the logs) sliced with the batch.
         Guided, on the step-kernel path, the chains run the whole batch's plans (_guided_weights), so split > 1 gives
@@ -521,6 +574,10 @@ class UNetEngine:
         guided = base is not None
         if keep is not None:
             keep = self.keep_operands(keep, x.shape, n, x.device)
+        if ref_bias5 is not None or ref_bias6 is not None:
+            self._map_check(x, s5, s6, ref_bias5, ref_bias6)
+            if not torch.cuda.is_current_stream_capturing():    # (a captured loop's static buffers were checked)
+                self.map_values_check(ref_bias5, ref_bias6)
         scale = None
         if guided:
             if len(base) != 4:
@@ -539,7 +596,7 @@ class UNetEngine:
             plan = self.split_plan(t_table, B, split) if split > 1 else None
         if not plan or len(plan) == 1:
             self._sample_call(solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6,
-                              base, scale, None, keep)
+                              base, scale, None, keep, ref_bias5=ref_bias5, ref_bias6=ref_bias6)
             return x
         per_step = x[0].numel() * B
         main = torch.cuda.current_stream(x.device)
@@ -566,8 +623,9 @@ class UNetEngine:
                 t_sub.record_stream(st)
             with torch.cuda.stream(st):
                 xs, a5, a6, x0l, epl, b5, b6, gb, gs, kc = cut(lo, hi)
+                c5, c6 = (None if v is None else v[lo:hi] for v in (ref_bias5, ref_bias6))   # the chain's maps
                 self._sample_call(solver, xs, a5, a6, t_sub, coef_table, eta, x0l, epl, per_step, k, b5, b6, gb, gs,
-                                  B if guided else None, kc)
+                                  B if guided else None, kc, ref_bias5=c5, ref_bias6=c6)
         for st in streams:
             main.wait_stream(st)
         return x
@@ -582,14 +640,18 @@ class GraphedDDIM:
     """A captured reverse loop with static buffers: replay() re-runs all n steps from x_init."""
 
     def __init__(self, engine, x_init, s5, s6, t_table, coef_table, eta, logs=True, split=1, solver="ddim",
-                 key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None):
+                 key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None,
+                 ref_bias6=None):
         """solver="ddim": coef_table [n,4] and eta, the reference's update; solver="msolver": coef_table [n,8]
         (ForwardDiffusion.multistep_coefs), eta unused and the x0 logs always kept (the solver's history).
         s5 / s6 may be stacked style references with key_bias5 / key_bias6 (UNetEngine.ddim_loop).
         base / guidance_scale: style guidance as in UNetEngine.ddim_loop; the strengths live in the static device
         buffer `scale` ([B] fp32), which set_guidance_scale() rewrites between replays without a new capture.
         keep: the regional keep as in UNetEngine.ddim_loop; its operands are cloned into static buffers, and
-        set_keep() rewrites the weights between replays without a new capture."""
+        set_keep() rewrites the weights between replays without a new capture.
+        ref_bias5 / ref_bias6: the style map as in UNetEngine.ddim_loop, cloned into static buffers that the captured
+        loop's attentions read; set_style_map() rewrites them between replays without a new capture and without a
+        prepare launch (the prepare phase does not read them)."""
         if solver not in ("ddim", "msolver"):
             raise ValueError(f"GraphedDDIM: unknown solver {solver!r}")
         self.solver = solver
@@ -603,6 +665,11 @@ class GraphedDDIM:
         self.s6 = s6.contiguous().clone()
         self.kb5 = None if key_bias5 is None else key_bias5.contiguous().clone()
         self.kb6 = None if key_bias6 is None else key_bias6.contiguous().clone()
+        self.rb5 = self.rb6 = None
+        if ref_bias5 is not None or ref_bias6 is not None:
+            engine._map_check(self.x, self.s5, self.s6, ref_bias5, ref_bias6)
+            engine.map_values_check(ref_bias5, ref_bias6)
+            self.rb5, self.rb6 = ref_bias5.clone(), ref_bias6.clone()
         self.base = self.scale = None
         if base is not None:
             self.base = tuple(None if v is None else ops.f32c(v).clone() for v in base)
@@ -646,7 +713,8 @@ class GraphedDDIM:
         self.engine._sample_call(self.solver, self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
                                  x0l, epl, per_step, self._slot + (k,), c(self.kb5), c(self.kb6), gb, c(self.scale),
                                  self.x.shape[0] if (split and gb is not None) else None,
-                                 self.engine._keep_cut(self.keep, lo, hi), phase=phase)
+                                 self.engine._keep_cut(self.keep, lo, hi), phase=phase, ref_bias5=c(self.rb5),
+                                 ref_bias6=c(self.rb6))
 
     def _operands(self):
         """The static tensors the prepare phase reads."""
@@ -707,11 +775,22 @@ class GraphedDDIM:
                                        self.x.device)
         self.keep[2].copy_(kp[2], non_blocking=False)
 
+    def set_style_map(self, ref_bias5, ref_bias6):
+        """Writes a new style map (UNetEngine.ddim_loop's ref_bias5 / ref_bias6) into the static buffers the captured
+        loop reads: the next replay runs under it.  No new capture and no prepare launch: the biases are not among the
+        prepare phase's operands.  Only for a graph captured with a style map."""
+        if self.rb5 is None:
+            raise ValueError("set_style_map: this loop was captured without a style map (ref_bias5= / ref_bias6=)")
+        self.engine._map_check(self.x, self.s5, self.s6, ref_bias5, ref_bias6)
+        self.engine.map_values_check(ref_bias5, ref_bias6)
+        self.rb5.copy_(ref_bias5, non_blocking=False)
+        self.rb6.copy_(ref_bias6, non_blocking=False)
+
     def replay(self):
         """Launches the loop graphs; the prepare graphs first when a static buffer the prepare phase reads (s5, s6,
         the key biases, the base maps and biases, t_table) or a UNet weight has been written through torch since the
         last prepare (compared by tensor version on the host), or after invalidate().  x_init, the coefficient
-        table, the guidance scale and the keep operands are read by the loop graphs: no prepare for them."""
+        table, the guidance scale, the keep operands and the style map are read by the loop graphs: no prepare for them."""
         wv = self.engine.weight_version()
         if wv != self._weight_version:
             self._build()

@@ -104,3 +104,37 @@ def mask_windows(mask, frames=512, overlap=64):
         if t1 > t0:
             out[n, 0, :, :t1 - t0] = mask[:, t0:t1]
     return out
+
+
+def style_map_windows(style_map, frames=512, overlap=64, n_mels=128):
+    """A recording's style map cut by window_plan exactly as the content is cut.  style_map [R, n_mels, T_total] (or
+    [R, T_total], broadcast over the n_mels mel bins): the non-negative weight of each of R style references at every
+    bin and frame.  Returns [N, R, n_mels, frames], window n holding frames [n * stride, n * stride + frames); frames at
+    or beyond T_total (a padded tail) repeat the last real frame: zeros there would leave a position without any
+    reference (LDM.style_map_bias wants a positive sum everywhere)."""
+    if not isinstance(style_map, torch.Tensor) or style_map.dim() not in (2, 3):
+        raise ValueError("style_map_windows: the map must be a tensor [R, n_mels, T_total] or [R, T_total]")
+    if style_map.dim() == 2:
+        style_map = style_map[:, None, :].expand(style_map.shape[0], int(n_mels), style_map.shape[1])
+    R, M, T_total = style_map.shape
+    if R < 1:
+        raise ValueError("style_map_windows: the map needs at least one reference")
+    N, stride = window_plan(T_total, frames, overlap)
+    t = torch.arange(N, device=style_map.device)[:, None] * stride + torch.arange(frames, device=style_map.device)[None, :]
+    t = t.clamp_(max=T_total - 1)                                # [N, frames]: the tail repeats the last real frame
+    return style_map[:, :, t].permute(2, 0, 1, 3).contiguous()   # [R, M, N, frames] -> [N, R, M, frames]
+
+
+def morph_map(R, T_total):
+    """[R, T_total] float64: a morph from the first of R references to the last along a recording of T_total frames.
+    Piecewise-linear triangular weights max(0, 1 - |u - r|) at u = t (R - 1) / (T_total - 1): frame 0 is all the first
+    reference, the last frame all the last, reference r peaks at its own knot, and every frame's weights sum to 1."""
+    R, T_total = int(R), int(T_total)
+    if R < 1 or T_total < 1:
+        raise ValueError(f"morph_map: need R >= 1 and T_total >= 1, got {R}, {T_total}")
+    if R == 1:
+        return torch.ones((1, T_total), dtype=torch.float64)
+    # t (R - 1) is an exact integer, and its quotient by T_total - 1 at the last frame is exactly R - 1
+    u = (torch.arange(T_total, dtype=torch.float64) * (R - 1)) / max(T_total - 1, 1)
+    w = (1.0 - (u[None, :] - torch.arange(R, dtype=torch.float64)[:, None]).abs()).clamp_(min=0.0)
+    return w / w.sum(0, keepdim=True)

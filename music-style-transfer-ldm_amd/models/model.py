@@ -430,7 +430,8 @@ class LDM(nn.Module):
         }
 
     # -------------------------------------------------------------------------------------------
-    def _reverse(self, z_t, style_embedding, times, eta, order=0, base_embedding=None, guidance_scale=1.0, keep=None):
+    def _reverse(self, z_t, style_embedding, times, eta, order=0, base_embedding=None, guidance_scale=1.0, keep=None,
+                 ref_bias=None):
         """The shared body of the samplers: len(times)-1 UNet + update steps in one C call.  order 0: the
         reference's DDIM-style update with eta; 1 / 2: the multistep solver of that order (eta unused).
 
@@ -440,7 +441,9 @@ class LDM(nn.Module):
         loop below is the unguided one.
 
         keep = (z0, n0, w, coefs): the regional keep (UNetEngine.ddim_loop).  After each step's update the state is
-        blended with coefs[i][0] z0 + coefs[i][1] n0 under the weights w [B,H,W]; the logs stay unblended."""
+        blended with coefs[i][0] z0 + coefs[i][1] n0 under the weights w [B,H,W]; the logs stay unblended.
+
+        ref_bias = (ref_bias5, ref_bias6): the style map's biases (style_map_bias; UNetEngine.ddim_loop)."""
         guided = not UNetEngine.is_unguided(base_embedding, guidance_scale)
         if guided:      # the checks, before anything runs
             if base_embedding is None:
@@ -483,6 +486,9 @@ class LDM(nn.Module):
             guide = {"base": base, "guidance_scale": scale}
         if keep is not None:
             guide["keep"] = keep
+        if ref_bias is not None:
+            mix = True
+            guide.update(ref_bias5=ref_bias[0].to(dev), ref_bias6=ref_bias[1].to(dev))
         if mix or guide:    # (the plain call stays the positional one)
             guide.update(key_bias5=kb5, key_bias6=kb6)
         with torch.no_grad():
@@ -530,6 +536,58 @@ class LDM(nn.Module):
         return out
 
     MAX_STYLE_REFS = 8
+
+    @staticmethod
+    def style_map_bias(style_map, H, W):
+        """A style map (which style where) as the reverse loop's reference biases for a latent of H x W.
+
+        style_map [B,R,n_mels,F] at spectrogram resolution (n_mels = 8 H, F = 8 W) or [B,R,H,W] at latent resolution:
+        the non-negative weight of each of R references at every position, with a positive sum over R everywhere
+        (ValueError otherwise, and for NaN / inf).  In float64 on the host: normalised per position to sum 1, averaged
+        over the cells of the two cross-attentions' token grids (CA2: H/4 x W/4, cells of 4 x 4 latent or 32 x 32
+        spectrogram positions; CA1: H/8 x W/8), then the log (0 becomes -inf: the reference is removed there).  The
+        average is taken by halving one axis at a time, (a + b) / 2, so a map that is constant over a cell keeps its
+        value exactly.  Returns (ref_bias5 [B,H*W/16,R], ref_bias6 [B,H*W/64,R]), fp32 on style_map's device, tokens
+        row-major as the UNet flattens its maps."""
+        H, W = int(H), int(W)
+        if H < 8 or W < 8 or H % 8 or W % 8:
+            raise ValueError(f"style_map_bias: the latent must be H x W with multiples of 8, got {H} x {W}")
+        if not isinstance(style_map, torch.Tensor) or style_map.dim() != 4 or style_map.shape[1] < 1 or \
+                tuple(style_map.shape[2:]) not in ((H, W), (8 * H, 8 * W)):
+            got = tuple(style_map.shape) if isinstance(style_map, torch.Tensor) else type(style_map).__name__
+            raise ValueError(f"style_map_bias: style_map must be [B,R,{8 * H},{8 * W}] (spectrogram) or [B,R,{H},{W}] "
+                             f"(latent), got {got}")
+        m = style_map.detach().to("cpu", torch.float64)
+        if not bool(torch.isfinite(m).all()) or bool((m < 0).any()):
+            raise ValueError("style_map_bias: style_map must be finite and non-negative")
+        tot = m.sum(1, keepdim=True)
+        if bool((tot <= 0).any()):
+            raise ValueError("style_map_bias: every position needs at least one reference of positive weight")
+        m = m / tot
+
+        def halve(t):     # 2 x 2 cells -> their mean, one axis at a time
+            t = (t[:, :, 0::2] + t[:, :, 1::2]) * 0.5
+            return (t[:, :, :, 0::2] + t[:, :, :, 1::2]) * 0.5
+
+        while m.shape[2] > H // 4:
+            m = halve(m)
+        out = []
+        for g in (m, halve(m)):
+            B, R, h, w = g.shape
+            out.append(torch.log(g).to(torch.float32).permute(0, 2, 3, 1).reshape(B, h * w, R).contiguous()
+                       .to(style_map.device))
+        return out[0], out[1]
+
+    def _map_biases(self, style_map, style_embedding, z_t):
+        """style_map_bias of a sampler call, after the checks against its embedding and latent."""
+        R = int(style_embedding.get("refs", 1)) if isinstance(style_embedding, dict) else 1
+        B, _, H, W = z_t.shape
+        if not isinstance(style_map, torch.Tensor) or style_map.dim() != 4 or style_map.shape[0] != B or \
+                style_map.shape[1] != R:
+            got = tuple(style_map.shape) if isinstance(style_map, torch.Tensor) else type(style_map).__name__
+            raise ValueError(f"style_map: need one map per sample and reference of the embedding, [{B},{R},...], got {got}")
+        rb5, rb6 = self.style_map_bias(style_map, H, W)
+        return rb5.to(z_t.device), rb6.to(z_t.device)
 
     @staticmethod
     def normalise_style_weights(weights, R, B=None):
@@ -635,11 +693,13 @@ class LDM(nn.Module):
                              f"{steps}, t_start {t_start} (with more steps than indices two times coincide)")
         return torch.linspace(t_start, 0, steps + 1).long()
 
-    def _solve(self, z_t, style_embedding, times, solver, eta, base_embedding=None, guidance_scale=1.0, keep=None):
+    def _solve(self, z_t, style_embedding, times, solver, eta, base_embedding=None, guidance_scale=1.0, keep=None,
+               style_map=None):
         if solver not in self._SOLVERS:
             raise ValueError(f"unknown solver {solver!r}: one of {sorted(self._SOLVERS)}")
+        rb = None if style_map is None else self._map_biases(style_map, style_embedding, z_t)
         return self._reverse(z_t, style_embedding, times, eta, self._SOLVERS[solver], base_embedding, guidance_scale,
-                             keep)
+                             keep, rb)
 
     @staticmethod
     def latent_keep(mask):
@@ -657,7 +717,8 @@ class LDM(nn.Module):
         return (z0, noise, keep, self.noise_scheduler.keep_coefs(times, exact_last))
 
     def style_conditioned_sample(self, z_t, style_embedding, steps=20, solver="dpmpp2m", t_start=None, eta=0.0,
-                                 guidance_scale=1.0, base_embedding=None, keep=None, z0=None, noise=None, exact_last=True):
+                                 guidance_scale=1.0, base_embedding=None, keep=None, z0=None, noise=None, exact_last=True,
+                                 style_map=None):
         """z_t at index t_start (default num_timesteps - 1) denoised in `steps` UNet passes over
         sample_times(t_start, steps).  solver: "dpmpp2m" (DPM-Solver++(2M), first-order first and last step),
         "dpmpp1" (its first-order form) or "ddim" (the reference's update, with eta, on this time grid).
@@ -670,15 +731,20 @@ class LDM(nn.Module):
 
         keep [B,H,W] in [0,1] with z0 and noise (z_t = q_sample(z0, t_start, noise)): the regional keep.  Where keep is
         1 the state is held on the content's own noising trajectory and ends as z0 (exact_last) or as z0 at index
-        0's noise level; where it is 0 the sampler runs free; values between blend the two after every step."""
+        0's noise level; where it is 0 the sampler runs free; values between blend the two after every step.
+
+        style_map [B,R,n_mels,F] or [B,R,H,W] (style_map_bias) with an embedding of R references (encode_styles): which
+        style where.  Reference r's weight at a query position is its map value there (normalised over R, averaged
+        over the attention's token cell), on top of the embedding's own weights; under guidance it applies to the
+        target only.  The fused engine only (RuntimeError on the per-layer path, as for a mix)."""
         t_start = self.num_timesteps - 1 if t_start is None else t_start
         times = self.sample_times(t_start, steps)
         kp = None if keep is None else self._keep_tuple(keep, z0, noise, times, exact_last)
-        return self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp)
+        return self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp, style_map)
 
     def content_style_transfer(self, content_spec, style_spec, t_start=99, steps=10, solver="dpmpp2m", noise=None,
                                eta=0.0, style_weights=None, guidance_scale=1.0, base_style=None, keep=None,
-                               composite=True):
+                               composite=True, style_map=None):
         """Encode content, q_sample it at index t_start (the strength), denoise over sample_times(t_start, steps)
         with `solver`, decode.  Returns (decoded, z_t_decoded) like content_style_transfer_wrapper.
 
@@ -697,9 +763,25 @@ class LDM(nn.Module):
         keep: a mask in [0,1] of what to leave as it is, [B,1,n_mels,F] at spectrogram resolution (reduced by
         latent_keep) or [B,H,W] at latent resolution: the regional keep with this call's own z_0 and noise.  composite
         (spectrogram-resolution masks): the decoded window becomes (1 - M) decoded + M content_spec, since the VAE is
-        lossy and a kept region should come back as it went in."""
+        lossy and a kept region should come back as it went in.
+
+        style_map [B,R,n_mels,F] (or [B,R,H,W] at latent resolution) with a 5-D style_spec of R references: which
+        style where (style_conditioned_sample).  It composes with style_weights (the weights multiply); a reference
+        that a zero of an [R] weight vector drops is dropped from the map too."""
         if style_weights is not None and style_spec.dim() != 5:
             raise ValueError("style_weights needs a 5-D style_spec [B,R,1,n_mels,F]")
+        if style_map is not None:      # the checks, before anything runs
+            if style_spec.dim() != 5:
+                raise ValueError("style_map needs a 5-D style_spec [B,R,1,n_mels,F]")
+            B, R = style_spec.shape[:2]
+            if not isinstance(style_map, torch.Tensor) or style_map.dim() != 4 or tuple(style_map.shape[:2]) != (B, R):
+                got = tuple(style_map.shape) if isinstance(style_map, torch.Tensor) else type(style_map).__name__
+                raise ValueError(f"style_map: need one map per sample and reference, [{B},{R},...], got {got}")
+            if style_weights is not None:
+                w = self.normalise_style_weights(style_weights, R, B)
+                if w.dim() == 1 and bool((w <= 0).any()):    # encode_styles drops these references: so does the map
+                    style_map = style_map[:, torch.nonzero(w > 0).flatten().to(style_map.device)]
+            self.style_map_bias(style_map, content_spec.shape[2] // 8, content_spec.shape[3] // 8)   # ValueError early
         content_spec = content_spec.float()
         style_spec = style_spec.float()
         times = self.sample_times(t_start, steps)
@@ -729,7 +811,7 @@ class LDM(nn.Module):
                                           z_t.device)
         style_embedding = self._style_embedding(style_spec, style_weights)
         if UNetEngine.is_unguided(base_style, guidance_scale):
-            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, keep=kp)
+            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, keep=kp, style_map=style_map)
         else:
             UNetEngine.guidance_scale(guidance_scale, content_spec.shape[0])   # (validated before anything runs)
             base_spec = content_spec if base_style is None else base_style.float()
@@ -737,7 +819,8 @@ class LDM(nn.Module):
             R = int(style_embedding.get("refs", 1)) if isinstance(style_embedding, dict) else 1
             if R > 1:
                 base_embedding = self.tile_embedding(base_embedding, R)
-            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp)
+            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp,
+                                     style_map)
         decoded = self.decoder(sampled, rescale=True)
         if mask is not None and composite:
             decoded = (1 - mask) * decoded + mask * content_spec

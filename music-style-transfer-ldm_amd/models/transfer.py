@@ -5,6 +5,7 @@ are crossfaded into one mel spectrogram that is vocoded once, so the phase is co
     python -m models.transfer --content a.wav --style b.wav --out c.wav [--checkpoint ldm.pth]
     python -m models.transfer --content a.wav --style b.wav c.wav --style-weights 0.7 0.3 --style-refs 2 --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --guidance-scale 2.5 --out o.wav
+    python -m models.transfer --content a.wav --style b.wav c.wav --solver dpmpp2m --style-morph --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --keep-band 0:200 --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
@@ -35,7 +36,7 @@ def style_window_indices(Ns, refs):
 def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, num_timesteps=100, eta=0.0,
                        batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None,
                        style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None, keep=None,
-                       composite=True):
+                       composite=True, style_map=None):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -65,8 +66,30 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     Regional transfer (needs a solver): keep is a mask [n_mels, T_total] in [0, 1] (longform.keep_mask) of what stays
     as it is.  It is cut into windows like the content (longform.mask_windows) and every window's sampler holds the
     kept region on the content's own noising trajectory (LDM.content_style_transfer); with composite the kept region
-    of every decoded window is the content window itself.  Composes with mixing and guidance."""
+    of every decoded window is the content window itself.  Composes with mixing and guidance.
+
+    Style map (needs a solver and style_refs = 1): style_map [recordings, n_mels, T_total] or [recordings, T_total]
+    (non-negative, a positive sum over the recordings everywhere; longform.morph_map makes a morph from the first
+    recording to the last) says which style applies where, per mel bin and frame.  It is cut into windows like the
+    content (longform.style_map_windows) and every window's sampler weighs the references per position
+    (LDM.content_style_transfer's style_map).  Composes with style_weights, guidance and keep."""
     n_mels = 128
+    if style_map is not None:
+        n_rec = len(style) if isinstance(style, (list, tuple)) else 1
+        if solver is None:
+            raise ValueError("transfer_recording: style_map needs a solver (the reference's sampler has no style map)")
+        if int(style_refs) != 1:
+            raise ValueError("transfer_recording: style_map needs style_refs = 1 (one map row per recording)")
+        style_map = torch.as_tensor(style_map)
+        T_map = 1 + content.numel() // HOP if content.dim() == 1 else -1
+        if style_map.dim() not in (2, 3) or style_map.shape[0] != n_rec or style_map.shape[-1] != T_map or \
+                (style_map.dim() == 3 and style_map.shape[1] != n_mels):
+            raise ValueError(f"transfer_recording: style_map must be [{n_rec}, {n_mels}, {T_map}] or [{n_rec}, {T_map}] "
+                             f"(one row per style recording), got {tuple(style_map.shape)}")
+        sm = style_map.detach().to(torch.float64)
+        if not bool(torch.isfinite(sm).all()) or bool((sm < 0).any()) or bool((sm.sum(0) <= 0).any()):
+            raise ValueError("transfer_recording: style_map must be finite and non-negative, with a positive sum over "
+                             "the recordings at every position")
     if keep is not None:
         if solver is None:
             raise ValueError("transfer_recording: keep needs a solver (the reference's sampler has no regional keep)")
@@ -95,7 +118,7 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     if not styles:
         raise ValueError("transfer_recording: no style recording")
     style_refs = int(style_refs)
-    mixing = len(styles) > 1 or style_refs != 1 or style_weights is not None
+    mixing = len(styles) > 1 or style_refs != 1 or style_weights is not None or style_map is not None
     if style_refs < 1 or len(styles) * style_refs > model.MAX_STYLE_REFS:
         raise ValueError(f"transfer_recording: {len(styles)} recordings x style_refs {style_refs} must give 1 to "
                          f"{model.MAX_STYLE_REFS} style windows")
@@ -130,10 +153,13 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     noise = noise.to(content.device)
 
     keep_w = None if keep is None else longform.mask_windows(keep, frames, overlap).to(content.device)
+    map_w = None if style_map is None else longform.style_map_windows(style_map, frames, overlap, n_mels)
 
     def guide_kw(b0, b1):
         """content_style_transfer's guidance and keep arguments for windows [b0, b1): none when neither is asked for."""
         kw = {} if keep_w is None else {"keep": keep_w[b0:b1], "composite": bool(composite)}
+        if map_w is not None:
+            kw["style_map"] = map_w[b0:b1]
         if not guided:
             return kw
         if isinstance(base_style, str):
@@ -232,6 +258,9 @@ def parse_args(argv=None):
                    help="the recording whose style is applied (.wav); several files are mixed")
     p.add_argument("--style-weights", type=float, nargs="+", default=None, dest="style_weights",
                    help="one non-negative weight per --style file (default equal)")
+    p.add_argument("--style-morph", action="store_true", dest="style_morph",
+                   help="morph from the first --style file to the last along the recording (needs --solver and at "
+                        "least two --style files): a style map of triangular weights over time")
     p.add_argument("--style-refs", type=int, default=1, dest="style_refs",
                    help="windows taken from each style recording, evenly spaced; with more than one window in all, "
                         "every content window attends over all of them")
@@ -269,6 +298,8 @@ def parse_args(argv=None):
         p.error(f"--style-weights: {len(args.style_weights)} weights for {len(args.style)} --style files")
     if args.style_refs < 1:
         p.error("--style-refs must be positive")
+    if args.style_morph and (args.solver is None or len(args.style) < 2 or args.style_refs != 1):
+        p.error("--style-morph needs --solver, at least two --style files and --style-refs 1")
     if not math.isfinite(args.guidance_scale):
         p.error("--guidance-scale must be finite")
     if (args.guidance_scale != 1.0 or args.base_style is not None) and args.solver is None:
@@ -302,6 +333,8 @@ def main(argv=None):
         guide["keep"] = longform.keep_mask(1 + content.numel() // HOP, 128, sr, times=args.keep_time,
                                            bands=args.keep_band, feather=args.keep_feather)
         guide["composite"] = args.composite
+    if args.style_morph:
+        guide["style_map"] = longform.morph_map(len(styles), 1 + content.numel() // HOP)
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
                              num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
                              solver=args.solver, t_start=args.t_start, style_weights=args.style_weights,
