@@ -409,6 +409,19 @@ typedef struct ldm_sample_args {
      * without its value fold.  They are the caller's buffers, read by every step's two attentions in the run phase:
      * ldm_sample_prepare does not read them, and the workspace size does not depend on them. */
     int32_t refs;
+    /* Joint sampling of overlapping windows (0 = off): batch rows b and b + 1 are neighbouring windows of one
+     * recording that share seam_cols latent columns, 0 <= seam_cols <= W / 2 (another value is an error).  One seam
+     * fuse replaces, for every b < B - 1, c, h and j in [0, seam_cols),
+     *     a = x[b,c,h,W-seam_cols+j];  q = x[b+1,c,h,j];  w_j = (j + 1) / (seam_cols + 1);  m = a + w_j * (q - a)
+     * (fp32, one rounding per operation: the division, d = q - a, p = w_j d, m = a + p) in both places by m.  The
+     * loop fuses once before step 0 and after every step's update (after the keep blend when there is one): nsteps + 1
+     * launches of one small kernel, and the returned x agrees bitwise across every seam.  The x0 / eps logs and the 2M
+     * history stay each window's own prediction.  Guided, the target and the base half of the doubled state are fused
+     * separately (no seam between them).  B == 1 is legal and launches nothing extra.  The rows of a joint loop are
+     * not independent: a caller that splits a batch into chains must not split a joint one.  With 0 every entry
+     * launches exactly what it launches without the field.  ldm_sample_prepare does not read the field, and the
+     * workspace size does not depend on it. */
+    int32_t seam_cols;
     float* x;                 /* [B,C,H,W], in place */
     const float *s5, *s6, *key_bias5, *key_bias6;
     const float *ref_bias5, *ref_bias6;
@@ -486,7 +499,9 @@ int ldm_sample_workspace_zeroed(const ldm_unet_shape* s, const ldm_unet_weights*
                                 int64_t* ranges);
 /* The guidance and the keep arithmetic on whole tensors.  ldm_guide_eps: out[i] = e_b[i] + scale[i / per_sample] *
  * (e_t[i] - e_b[i]) for B * per_sample elements (out may alias e_t or e_b).  ldm_keep_blend: in place on x (NCHW),
- * with one row coef = {a, b}. */
+ * with one row coef = {a, b}.  ldm_seam_fuse: one seam fuse of ldm_sample_args.seam_cols in place on x (NCHW),
+ * 1 <= seam_cols <= W / 2; B == 1 launches nothing. */
+int ldm_seam_fuse(float* x, int32_t B, int32_t C, int32_t H, int32_t W, int32_t seam_cols, void* stream);
 int ldm_guide_eps(const float* e_t, const float* e_b, const float* scale, int64_t per_sample, int32_t B, float* out,
                   void* stream);
 int ldm_keep_blend(float* x, const float* z0, const float* n0, const float* keep, const float* coef, int32_t B, int32_t C,

@@ -290,6 +290,8 @@ int step_ks_mask();   // layers running the K-split step form (LDM_UCONV_KS)
 #define LDM_DEBUG_BOUNDS 0
 #endif
 int step_layout(const float* x, float* y, int B, int C, int HW, bool to_nhwc, hipStream_t st);
+// seam.hip: the joint loop's seam fuse on `groups` stacks of B neighbouring windows, in place
+int seam_fuse(float* x, int groups, int B, int C, int H, int W, int ov, bool nhwc, hipStream_t st);
 
 // wgrad.hip: the tap-shared weight-gradient kernel (ldm_conv_backward_weight where it applies)
 bool wgrad2_plan_ws(const ldm_conv_desc& d, int64_t& ws_floats);

@@ -675,6 +675,13 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
     const size_t cw = msolver ? 8 : 4;   // floats per coefficient row
     const int HW = s->H * s->W;
     const RefBias* rb = lp.map ? &lp.rb : nullptr;
+    // Joint sampling (seam_cols > 0, B > 1): the batch rows are neighbouring windows, fused across their seams before
+    // step 0 and after every step's update (seam.hip).  Guided, each half of the doubled state on its own.  Off, nothing
+    // is launched and the loops below are the ones they always were.
+    const int seam = sc->B > 1 ? a.seam_cols : 0;
+    auto fuse_seams = [&](float* xstate, bool nhwc) -> int {
+        return seam ? seam_fuse(xstate, g ? 2 : 1, sc->B, s->C, s->H, s->W, seam, nhwc, st) : 0;
+    };
     auto make_fuse = [&](int i, float* xstate) {
         DdimFuse fuse{coef_table + cw * (size_t)i, eta, xstate, x0_logs ? x0_logs + (size_t)i * n : nullptr,
                       eps_logs ? eps_logs + (size_t)i * n : nullptr, msolver,
@@ -700,6 +707,7 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
                                g ? g->scale : nullptr, krows, sc->B, nr);
             LDM_CHECK_LAUNCH("keep_rows_kernel");
         }
+        LDM_TRY(fuse_seams(ws.xs, true));
         for (int i = 0; i < nsteps; ++i) {
             DdimFuse fuse = make_fuse(i, ws.xs);
             if (kp) {
@@ -707,6 +715,7 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
                 if (g) fuse.eb = kreg;   // e_b leads the keep region
             }
             LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold, rb));
+            LDM_TRY(fuse_seams(ws.xs, true));
         }
         return step_layout(ws.xs, x, sc->B, s->C, HW, false, st);
     }
@@ -716,6 +725,7 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
         LDM_TRY(concat_halves(x, x, ws.xs, 1, dense, st));
         xstate = ws.xs;
     }
+    LDM_TRY(fuse_seams(xstate, false));
     for (int i = 0; i < nsteps; ++i) {
         // noise_pred = unet(x, t, style_embedding)                                (model.py:439)
         // and, fused into dec1's epilogue, the x0 / direction / eta update and the two log clones
@@ -726,6 +736,7 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
         else
             LDM_TRY(unet_forward(*s, *w, xstate, t_table + (size_t)i * sc->B, 0, s5, s6, nullptr, ws, st,
                                  temb_all + (size_t)i * s->B * 128, &fuse, /*kv_ready=*/true));
+        LDM_TRY(fuse_seams(xstate, false));
     }
     if (g) LDM_HIP_TRY(hipMemcpyAsync(x, ws.xs, (size_t)dense * 4, hipMemcpyDeviceToDevice, st));
     return 0;
@@ -798,6 +809,7 @@ static int sample_check(const ldm_unet_shape* s, const ldm_unet_weights* w, cons
                 "sample: null argument");
     LDM_REQUIRE(a->nsteps >= 0, "sample: negative step count");
     LDM_REQUIRE(a->S5 >= 0 && a->S6 >= 0, "sample: negative key count");
+    LDM_REQUIRE(a->seam_cols >= 0 && a->seam_cols <= s->W / 2, "sample: seam_cols must lie in [0, W / 2]");
     const bool guided = guidance_on(*a), keep = keep_on(*a);
     if (guided) {
         LDM_REQUIRE(a->s5_base && a->s6_base, "guided sample: null base style maps");

@@ -76,7 +76,7 @@ SOLVER = {"ddim": 0, "msolver": 1}   # ldm_capi.h LDM_SOLVER_*
 class SampleArgs(ctypes.Structure):
     """ldm_sample_args: the reverse loop's operands and options (NULL / 0 = off); semantics in ldm_capi.h."""
     _fields_ = [("solver", c_int32), ("nsteps", c_int32), ("eta", c_float), ("S5", c_int32), ("S6", c_int32),
-                ("refs", c_int32),
+                ("refs", c_int32), ("seam_cols", c_int32),
                 ("x", c_fp), ("s5", c_fp), ("s6", c_fp), ("key_bias5", c_fp), ("key_bias6", c_fp),
                 ("ref_bias5", c_fp), ("ref_bias6", c_fp),
                 ("s5_base", c_fp), ("s6_base", c_fp), ("key_bias5_base", c_fp), ("key_bias6_base", c_fp),
@@ -230,6 +230,8 @@ SIGNATURES = {
                                                 c_int32, c_int32, c_int32, c_int32, c_vp]),
     "ldm_guide_eps": (c_int32, [c_fp, c_fp, c_fp, c_int64, c_int32, c_fp, c_vp]),
     "ldm_keep_blend": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_int64, c_vp]),
+    # joint sampling of overlapping windows (seam.hip): one seam fuse on an NCHW state
+    "ldm_seam_fuse": (c_int32, [c_fp, c_int32, c_int32, c_int32, c_int32, c_int32, c_vp]),
     # backward / optimiser
     "ldm_conv_tiled_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),
     "ldm_conv_sconv_plan": (c_int32, [ctypes.POINTER(ConvDesc), c_int32, ctypes.POINTER(ConvPlan)]),

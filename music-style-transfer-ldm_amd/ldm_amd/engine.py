@@ -466,6 +466,15 @@ class UNetEngine:
                     key_bias5_base=p5b, key_bias6_base=p6b, guide_scale=scale.data_ptr())
 
     @staticmethod
+    def seam_check(seam_cols, W):
+        """The joint loop's seam width as an int: 0 (off) or latent columns in [1, W / 2].  ValueError otherwise."""
+        ov = int(seam_cols)
+        if ov != seam_cols or not 0 <= ov <= int(W) // 2:
+            raise ValueError(f"seam_cols must be a whole number of latent columns in [0, W / 2] = [0, {int(W) // 2}], "
+                             f"got {seam_cols!r}")
+        return ov
+
+    @staticmethod
     def _single_maps_check(x, s5, s6):
         B, C, H, W = x.shape
         if tuple(s5.shape) != (B, 256, H // 4, W // 4) or tuple(s6.shape) != (B, 512, H // 8, W // 8):
@@ -474,12 +483,13 @@ class UNetEngine:
 
     def _sample_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
                      key_bias5=None, key_bias6=None, base=None, scale=None, plan_batch=None, keep=None, phase=None,
-                     ref_bias5=None, ref_bias6=None):
+                     ref_bias5=None, ref_bias6=None, seam_cols=0):
         """One C loop (ldm_sample) of solver "ddim" / "msolver" on x, with whichever options are given: a mix (stacked
         s5 / s6, key biases), guidance (base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the target's key
         counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights) and the regional
         keep (keep_operands()).  ref_bias5 / ref_bias6: the style map's biases (ddim_loop); their layout is checked here,
-        their values by the callers (no device work in this function: it runs under capture).
+        their values by the callers (no device work in this function: it runs under capture).  seam_cols: the joint
+        loop's seam width (ddim_loop; checked by seam_check).
 
         phase None: the whole loop (ldm_sample).  phase "prepare" / "run": that C entry alone (GraphedDDIM, on
         workspaces of its own: the engine's shared ones are also written by forward() and by captured graphs' replays,
@@ -490,7 +500,7 @@ class UNetEngine:
         a = L.SampleArgs(solver=L.SOLVER[solver], nsteps=n, eta=float(eta), x=x.data_ptr(), s5=s5.data_ptr(),
                          s6=s6.data_ptr(), t_table=t_table.data_ptr(), coef_table=coef_table.data_ptr(),
                          x0_logs=ops._p(x0_logs), eps_logs=ops._p(eps_logs), log_step_stride=int(log_stride),
-                         stream=ops.stream_handle())
+                         stream=ops.stream_handle(), seam_cols=self.seam_check(seam_cols, W))
         if base is not None:
             for f, v in self._guided_operands(x, s5, s6, key_bias5, key_bias6, base, scale).items():
                 setattr(a, f, v)
@@ -514,22 +524,23 @@ class UNetEngine:
         L.call(entry, byref(shape), byref(w), byref(a))
 
     def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None, key_bias5=None,
-                     key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None, ref_bias6=None):
+                     key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None, ref_bias6=None,
+                     seam_cols=0):
         """ddim_loop's twin for the multistep solver (DPM-Solver++(2M) or its first-order form): coef_table
         [n,8] from ForwardDiffusion.multistep_coefs (device), no eta.  x0_logs [n,B,C,H,W] is required: step i
-        reads step i-1's slot as its history.  Same sub-batch chains, base=, guidance_scale=, keep= and style map
-        (ref_bias5= / ref_bias6=) as ddim_loop."""
+        reads step i-1's slot as its history.  Same sub-batch chains, base=, guidance_scale=, keep=, style map
+        (ref_bias5= / ref_bias6=) and seam_cols= as ddim_loop."""
         if x0_logs is None:
             raise ValueError("msolver_loop: x0_logs is required (it is the solver's history)")
         if coef_table.dim() != 2 or coef_table.shape[1] != 8 or coef_table.shape[0] != t_table.shape[0]:
             raise ValueError(f"msolver_loop: coef_table must be [n,8] for n = {t_table.shape[0]} steps, "
                              f"got {tuple(coef_table.shape)}")
         return self._loop("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, split, plan, key_bias5,
-                          key_bias6, base, guidance_scale, keep, ref_bias5, ref_bias6)
+                          key_bias6, base, guidance_scale, keep, ref_bias5, ref_bias6, seam_cols)
 
     def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None,
                   key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None,
-                  ref_bias6=None):
+                  ref_bias6=None, seam_cols=0):
         """In-place reverse loop on x ([B,C,H,W] contiguous fp32).  t_table [n,B] int64, coef [n,4] (device).
 
         Style mixing: s5 / s6 may hold R style references stacked along the map's height (s5 [B,256,R*H/4,W/4],
@@ -555,16 +566,24 @@ class UNetEngine:
         to the key biases, apply to the target half only under guidance, and are read by every step's attentions, not
         folded before the loop.  ValueError for a wrong shape, dtype or device and for NaN / +inf.
 
+        Joint sampling: seam_cols (latent columns, 0 = off, at most W / 2) declares the batch rows neighbouring windows
+        of one recording, row b + 1 starting seam_cols columns before row b ends.  Before step 0 and after every
+        step's update (after the keep blend) the columns two rows share are replaced in both by one weighted average,
+        a + w_j (q - a) with w_j = (j + 1) / (seam_cols + 1) the later window's weight (ldm_capi.h), so all rows carry
+        one consistent latent canvas and the returned x agrees bitwise across every seam.  The logs stay each
+        window's own prediction; under guidance the two halves are fused separately.  The rows are then not
+        independent: split > 1 or a multi-chain plan with seam_cols > 0 is a ValueError.  B = 1 is the plain loop.
+
         split > 1 runs the batch as that many independent sub-batch chains, each on its own stream
         (forked from and joined back into the current stream, so it also works under graph capture).
         The path is per-sample, so the result is the same up to fp32 summation order (a sub-batch
         size may get a conv plan that splits K differently); the chains' launch and memory latencies
         overlap each other's work."""
         return self._loop("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, split, plan, key_bias5,
-                          key_bias6, base, guidance_scale, keep, ref_bias5, ref_bias6)
+                          key_bias6, base, guidance_scale, keep, ref_bias5, ref_bias6, seam_cols)
 
     def _loop(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, split, plan, key_bias5=None,
-              key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None, ref_bias6=None):
+              key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None, ref_bias6=None, seam_cols=0):
         """The whole batch in one _sample_call, or one per sub-batch chain with every per-sample operand (the maps, the
         biases, the base, the scales, the keep operands, the logs) sliced with the batch.
         Guided, on the step-kernel path, the chains run the whole batch's plans (_guided_weights), so split > 1 gives
@@ -572,6 +591,10 @@ class UNetEngine:
         fold applies up to a doubled batch of 8)."""
         B, n = x.shape[0], t_table.shape[0]
         guided = base is not None
+        seam_cols = self.seam_check(seam_cols, x.shape[3])
+        if seam_cols and (split > 1 or (plan and len(plan) > 1)):
+            raise ValueError("seam_cols: the rows of a joint loop are fused across their seams after every step, so the "
+                             "batch cannot run as independent sub-batch chains (split > 1 or a multi-chain plan)")
         if keep is not None:
             keep = self.keep_operands(keep, x.shape, n, x.device)
         if ref_bias5 is not None or ref_bias6 is not None:
@@ -596,7 +619,7 @@ class UNetEngine:
             plan = self.split_plan(t_table, B, split) if split > 1 else None
         if not plan or len(plan) == 1:
             self._sample_call(solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6,
-                              base, scale, None, keep, ref_bias5=ref_bias5, ref_bias6=ref_bias6)
+                              base, scale, None, keep, ref_bias5=ref_bias5, ref_bias6=ref_bias6, seam_cols=seam_cols)
             return x
         per_step = x[0].numel() * B
         main = torch.cuda.current_stream(x.device)
@@ -641,7 +664,7 @@ class GraphedDDIM:
 
     def __init__(self, engine, x_init, s5, s6, t_table, coef_table, eta, logs=True, split=1, solver="ddim",
                  key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None,
-                 ref_bias6=None):
+                 ref_bias6=None, seam_cols=0):
         """solver="ddim": coef_table [n,4] and eta, the reference's update; solver="msolver": coef_table [n,8]
         (ForwardDiffusion.multistep_coefs), eta unused and the x0 logs always kept (the solver's history).
         s5 / s6 may be stacked style references with key_bias5 / key_bias6 (UNetEngine.ddim_loop).
@@ -651,9 +674,13 @@ class GraphedDDIM:
         set_keep() rewrites the weights between replays without a new capture.
         ref_bias5 / ref_bias6: the style map as in UNetEngine.ddim_loop, cloned into static buffers that the captured
         loop's attentions read; set_style_map() rewrites them between replays without a new capture and without a
-        prepare launch (the prepare phase does not read them)."""
+        prepare launch (the prepare phase does not read them).
+        seam_cols: joint sampling as in UNetEngine.ddim_loop (the fuses are captured with the loop; not with split > 1)."""
         if solver not in ("ddim", "msolver"):
             raise ValueError(f"GraphedDDIM: unknown solver {solver!r}")
+        self.seam_cols = engine.seam_check(seam_cols, x_init.shape[3])
+        if self.seam_cols and split > 1:
+            raise ValueError("GraphedDDIM: seam_cols needs split = 1 (the rows of a joint loop are not independent)")
         self.solver = solver
         logs = logs or solver == "msolver"
         self.engine = engine
@@ -714,7 +741,7 @@ class GraphedDDIM:
                                  x0l, epl, per_step, self._slot + (k,), c(self.kb5), c(self.kb6), gb, c(self.scale),
                                  self.x.shape[0] if (split and gb is not None) else None,
                                  self.engine._keep_cut(self.keep, lo, hi), phase=phase, ref_bias5=c(self.rb5),
-                                 ref_bias6=c(self.rb6))
+                                 ref_bias6=c(self.rb6), seam_cols=self.seam_cols)
 
     def _operands(self):
         """The static tensors the prepare phase reads."""

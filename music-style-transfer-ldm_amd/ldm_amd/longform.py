@@ -43,6 +43,22 @@ def stitch_windows(y, ref_db, overlap, T_total, max_db=80, return_db=False):
     return ops.mel_stitch(y, ref_db, overlap, T_total, max_db, return_db)
 
 
+def noise_windows(N, C, H, W, ov, seed):
+    """The q_sample noise of N neighbouring latent windows [N, C, H, W] that share `ov` latent columns (0 <= ov <=
+    W / 2), cut from one canvas: one CPU draw [C, H, (N - 1)(W - ov) + W] from torch.Generator().manual_seed(seed),
+    window n holding its columns [n (W - ov), n (W - ov) + W).  Neighbours therefore share their overlap's noise,
+    noise[n, :, :, W-ov:] == noise[n+1, :, :, :ov], whatever batch size the windows are later grouped by (joint
+    sampling).  CPU fp32."""
+    N, C, H, W, ov = int(N), int(C), int(H), int(W), int(ov)
+    if N < 1 or C < 1 or H < 1 or W < 1:
+        raise ValueError(f"noise_windows: need N, C, H, W >= 1, got {N}, {C}, {H}, {W}")
+    if not 0 <= ov <= W // 2:
+        raise ValueError(f"noise_windows: ov must lie in [0, W / 2], got {ov} for W {W}")
+    stride = W - ov
+    canvas = torch.randn((C, H, (N - 1) * stride + W), generator=torch.Generator().manual_seed(int(seed)))
+    return torch.stack([canvas[:, :, n * stride:n * stride + W] for n in range(N)]).contiguous()
+
+
 def _keep_profile(n, lo, hi, feather):
     """[n] float64: 1 on indices [lo, hi] (clipped to the axis), 0 elsewhere, with a linear ramp over the `feather`
     outermost indices inside each edge, (d + 1) / (feather + 1) at distance d from the edge.  An edge that is the

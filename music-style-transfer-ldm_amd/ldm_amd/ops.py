@@ -1017,6 +1017,22 @@ def keep_blend_(x, z0, n0, keep, coef):
     return x
 
 
+def seam_fuse_(x, seam_cols):
+    """One seam fuse of a joint loop on whole tensors, in place on x (ldm_seam_fuse).  The rows of x [B,C,H,W]
+    (contiguous fp32) are neighbouring windows sharing seam_cols latent columns, 1 <= seam_cols <= W / 2: for every
+    b < B - 1 and j < seam_cols, x[b,:,:,W-seam_cols+j] and x[b+1,:,:,j] both become a + w_j (q - a) with
+    w_j = (j + 1) / (seam_cols + 1), per element in fp32, one rounding per operation.  B = 1 leaves x as it is."""
+    require_device(x)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("seam_fuse: x must be a contiguous fp32 [B,C,H,W] tensor")
+    B, C, H, W = x.shape
+    seam_cols = int(seam_cols)
+    if not 1 <= seam_cols <= W // 2:
+        raise ValueError(f"seam_fuse: seam_cols must lie in [1, W / 2] = [1, {W // 2}], got {seam_cols}")
+    L.call("ldm_seam_fuse", x.data_ptr(), B, C, H, W, seam_cols, stream_handle())
+    return x
+
+
 def guide_eps(e_t, e_b, scale, out=None):
     """Style guidance on whole noise predictions (ldm_guide_eps): e_b + scale[b] * (e_t - e_b) per element in fp32,
     one rounding per operation.  e_t / e_b [B, ...] contiguous fp32, scale a device fp32 [B] tensor."""

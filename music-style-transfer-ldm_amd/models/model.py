@@ -431,7 +431,7 @@ class LDM(nn.Module):
 
     # -------------------------------------------------------------------------------------------
     def _reverse(self, z_t, style_embedding, times, eta, order=0, base_embedding=None, guidance_scale=1.0, keep=None,
-                 ref_bias=None):
+                 ref_bias=None, seam_cols=0):
         """The shared body of the samplers: len(times)-1 UNet + update steps in one C call.  order 0: the
         reference's DDIM-style update with eta; 1 / 2: the multistep solver of that order (eta unused).
 
@@ -443,7 +443,11 @@ class LDM(nn.Module):
         keep = (z0, n0, w, coefs): the regional keep (UNetEngine.ddim_loop).  After each step's update the state is
         blended with coefs[i][0] z0 + coefs[i][1] n0 under the weights w [B,H,W]; the logs stay unblended.
 
-        ref_bias = (ref_bias5, ref_bias6): the style map's biases (style_map_bias; UNetEngine.ddim_loop)."""
+        ref_bias = (ref_bias5, ref_bias6): the style map's biases (style_map_bias; UNetEngine.ddim_loop).
+
+        seam_cols: joint sampling (UNetEngine.ddim_loop): the rows of z_t are neighbouring windows sharing that many
+        latent columns, fused before step 0 and after every step.  The engine is called without a split."""
+        seam_cols = UNetEngine.seam_check(seam_cols, z_t.shape[3])
         guided = not UNetEngine.is_unguided(base_embedding, guidance_scale)
         if guided:      # the checks, before anything runs
             if base_embedding is None:
@@ -489,6 +493,8 @@ class LDM(nn.Module):
         if ref_bias is not None:
             mix = True
             guide.update(ref_bias5=ref_bias[0].to(dev), ref_bias6=ref_bias[1].to(dev))
+        if seam_cols and B > 1:
+            guide["seam_cols"] = seam_cols
         if mix or guide:    # (the plain call stays the positional one)
             guide.update(key_bias5=kb5, key_bias6=kb6)
         with torch.no_grad():
@@ -504,6 +510,8 @@ class LDM(nn.Module):
                                        "style map per sample (the fused engine needs a multiple of 8, at least 16)")
                 emb = {"s5": s5, "s6": s6}
                 emb_b = {"s5": base[0], "s6": base[1]} if guided else None
+                if seam_cols and B > 1:     # the stand-alone fuse: before step 0, then after every step
+                    ops.seam_fuse_(x, seam_cols)
                 for i in range(n):
                     eps = self.unet(x, t_table[i], emb)
                     if guided:      # the second UNet call of the step, then the guidance kernel
@@ -515,6 +523,8 @@ class LDM(nn.Module):
                         ops.ddim_step_(x, eps, coefs[i].contiguous(), float(eta), x0_logs[i], eps_logs[i])
                     if keep is not None:    # the stand-alone blend, after the update kernel
                         ops.keep_blend_(x, keep[0], keep[1], keep[2], keep[3][i])
+                    if seam_cols and B > 1:
+                        ops.seam_fuse_(x, seam_cols)
         logs["timesteps"] = [int(v) for v in times[:-1]]
         logs["pred_x0"] = list(x0_logs.unbind(0))
         logs["noise_pred"] = list(eps_logs.unbind(0))
@@ -694,12 +704,28 @@ class LDM(nn.Module):
         return torch.linspace(t_start, 0, steps + 1).long()
 
     def _solve(self, z_t, style_embedding, times, solver, eta, base_embedding=None, guidance_scale=1.0, keep=None,
-               style_map=None):
+               style_map=None, seam_cols=0):
         if solver not in self._SOLVERS:
             raise ValueError(f"unknown solver {solver!r}: one of {sorted(self._SOLVERS)}")
         rb = None if style_map is None else self._map_biases(style_map, style_embedding, z_t)
         return self._reverse(z_t, style_embedding, times, eta, self._SOLVERS[solver], base_embedding, guidance_scale,
-                             keep, rb)
+                             keep, rb, seam_cols)
+
+    @classmethod
+    def _seam_cols(cls, seam_overlap, frames, solver):
+        """A joint call's seam width in latent columns from the overlap in mel frames, after the checks."""
+        ov = int(seam_overlap)
+        if ov != seam_overlap or ov < 0:
+            raise ValueError(f"seam_overlap must be a non-negative whole number of mel frames, got {seam_overlap!r}")
+        if ov == 0:
+            return 0
+        if solver not in cls._SOLVERS:
+            raise ValueError(f"seam_overlap needs a solver, one of {sorted(cls._SOLVERS)} (got {solver!r})")
+        if ov % 8:
+            raise ValueError(f"seam_overlap must be a multiple of 8 mel frames (one latent column), got {ov}")
+        if ov > int(frames) // 2:
+            raise ValueError(f"seam_overlap must be at most frames / 2 = {int(frames) // 2}, got {ov}")
+        return ov // 8
 
     @staticmethod
     def latent_keep(mask):
@@ -718,7 +744,7 @@ class LDM(nn.Module):
 
     def style_conditioned_sample(self, z_t, style_embedding, steps=20, solver="dpmpp2m", t_start=None, eta=0.0,
                                  guidance_scale=1.0, base_embedding=None, keep=None, z0=None, noise=None, exact_last=True,
-                                 style_map=None):
+                                 style_map=None, seam_cols=0):
         """z_t at index t_start (default num_timesteps - 1) denoised in `steps` UNet passes over
         sample_times(t_start, steps).  solver: "dpmpp2m" (DPM-Solver++(2M), first-order first and last step),
         "dpmpp1" (its first-order form) or "ddim" (the reference's update, with eta, on this time grid).
@@ -736,15 +762,21 @@ class LDM(nn.Module):
         style_map [B,R,n_mels,F] or [B,R,H,W] (style_map_bias) with an embedding of R references (encode_styles): which
         style where.  Reference r's weight at a query position is its map value there (normalised over R, averaged
         over the attention's token cell), on top of the embedding's own weights; under guidance it applies to the
-        target only.  The fused engine only (RuntimeError on the per-layer path, as for a mix)."""
+        target only.  The fused engine only (RuntimeError on the per-layer path, as for a mix).
+
+        seam_cols (latent columns, 0 = off, at most W / 2): joint sampling of overlapping windows.  The rows of z_t are
+        neighbouring windows of one recording, row b + 1 starting seam_cols columns before row b ends; the columns two
+        rows share are replaced in both by one weighted average before step 0 and after every step
+        (UNetEngine.ddim_loop), so the returned x agrees bitwise across every seam.  The logs stay each window's own."""
         t_start = self.num_timesteps - 1 if t_start is None else t_start
         times = self.sample_times(t_start, steps)
         kp = None if keep is None else self._keep_tuple(keep, z0, noise, times, exact_last)
-        return self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp, style_map)
+        return self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp, style_map,
+                           seam_cols)
 
     def content_style_transfer(self, content_spec, style_spec, t_start=99, steps=10, solver="dpmpp2m", noise=None,
                                eta=0.0, style_weights=None, guidance_scale=1.0, base_style=None, keep=None,
-                               composite=True, style_map=None):
+                               composite=True, style_map=None, seam_overlap=0):
         """Encode content, q_sample it at index t_start (the strength), denoise over sample_times(t_start, steps)
         with `solver`, decode.  Returns (decoded, z_t_decoded) like content_style_transfer_wrapper.
 
@@ -767,7 +799,14 @@ class LDM(nn.Module):
 
         style_map [B,R,n_mels,F] (or [B,R,H,W] at latent resolution) with a 5-D style_spec of R references: which
         style where (style_conditioned_sample).  It composes with style_weights (the weights multiply); a reference
-        that a zero of an [R] weight vector drops is dropped from the map too."""
+        that a zero of an [R] weight vector drops is dropped from the map too.
+
+        seam_overlap (mel frames, 0 = off): joint sampling.  The rows of content_spec are neighbouring windows of one
+        recording that share seam_overlap frames (longform.window_plan's overlap); the sampler fuses the seam_overlap / 8
+        latent columns they share after every step (style_conditioned_sample's seam_cols).  A multiple of 8, at most
+        frames / 2, and it needs a solver (ValueError otherwise).  For the windows to describe one canvas from the
+        start, pass `noise` from longform.noise_windows."""
+        seam_cols = self._seam_cols(seam_overlap, content_spec.shape[3], solver)
         if style_weights is not None and style_spec.dim() != 5:
             raise ValueError("style_weights needs a 5-D style_spec [B,R,1,n_mels,F]")
         if style_map is not None:      # the checks, before anything runs
@@ -811,7 +850,8 @@ class LDM(nn.Module):
                                           z_t.device)
         style_embedding = self._style_embedding(style_spec, style_weights)
         if UNetEngine.is_unguided(base_style, guidance_scale):
-            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, keep=kp, style_map=style_map)
+            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, keep=kp, style_map=style_map,
+                                     seam_cols=seam_cols)
         else:
             UNetEngine.guidance_scale(guidance_scale, content_spec.shape[0])   # (validated before anything runs)
             base_spec = content_spec if base_style is None else base_style.float()
@@ -820,7 +860,7 @@ class LDM(nn.Module):
             if R > 1:
                 base_embedding = self.tile_embedding(base_embedding, R)
             sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp,
-                                     style_map)
+                                     style_map, seam_cols)
         decoded = self.decoder(sampled, rescale=True)
         if mask is not None and composite:
             decoded = (1 - mask) * decoded + mask * content_spec

@@ -7,6 +7,7 @@ are crossfaded into one mel spectrogram that is vocoded once, so the phase is co
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --guidance-scale 2.5 --out o.wav
     python -m models.transfer --content a.wav --style b.wav c.wav --solver dpmpp2m --style-morph --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --keep-band 0:200 --out o.wav
+    python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --joint --batch 16 --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
 """
@@ -36,7 +37,7 @@ def style_window_indices(Ns, refs):
 def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, num_timesteps=100, eta=0.0,
                        batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None,
                        style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None, keep=None,
-                       composite=True, style_map=None):
+                       composite=True, style_map=None, joint=False):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -72,8 +73,24 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     (non-negative, a positive sum over the recordings everywhere; longform.morph_map makes a morph from the first
     recording to the last) says which style applies where, per mel bin and frame.  It is cut into windows like the
     content (longform.style_map_windows) and every window's sampler weighs the references per position
-    (LDM.content_style_transfer's style_map).  Composes with style_weights, guidance and keep."""
+    (LDM.content_style_transfer's style_map).  Composes with style_weights, guidance and keep.
+
+    Joint sampling (joint=True; needs a solver and an overlap that is a multiple of 8): the windows of a model call are
+    denoised as one latent canvas.  The q_sample noise comes from longform.noise_windows (one canvas draw seeded with
+    `seed`, so neighbours share their overlap's noise) instead of the per-window rows, and every group of batch_size
+    consecutive windows goes through LDM.content_style_transfer with seam_overlap=overlap: after every step the
+    latent columns two neighbours share are replaced in both by one weighted average, and the crossfade then meets
+    two decodings of the same latent instead of two independent samples.  The seam between two groups is not fused
+    (its windows only share the canvas noise): batch_size >= N gives one coherent canvas.  Beyond 8 windows per call
+    the sampler's bottleneck runs without its value fold (slower per window, the same results up to rounding).
+    Composes with mixing, guidance, keep and the style map.  joint=False is the call it always was."""
     n_mels = 128
+    if joint:
+        if solver is None:
+            raise ValueError("transfer_recording: joint needs a solver (the reference's sampler has no seam fuse)")
+        if int(overlap) % 8:
+            raise ValueError(f"transfer_recording: joint needs an overlap that is a multiple of 8 mel frames (whole "
+                             f"latent columns), got {overlap}")
     if style_map is not None:
         n_rec = len(style) if isinstance(style, (list, tuple)) else 1
         if solver is None:
@@ -149,7 +166,10 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     xs = xs[:Ns]
 
     latent = model.unet.enc1.weight.shape[1]
-    noise = torch.randn((N, latent, n_mels // 8, frames // 8), generator=torch.Generator().manual_seed(int(seed)))
+    if joint:
+        noise = longform.noise_windows(N, latent, n_mels // 8, frames // 8, overlap // 8, seed)
+    else:
+        noise = torch.randn((N, latent, n_mels // 8, frames // 8), generator=torch.Generator().manual_seed(int(seed)))
     noise = noise.to(content.device)
 
     keep_w = None if keep is None else longform.mask_windows(keep, frames, overlap).to(content.device)
@@ -158,6 +178,8 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     def guide_kw(b0, b1):
         """content_style_transfer's guidance and keep arguments for windows [b0, b1): none when neither is asked for."""
         kw = {} if keep_w is None else {"keep": keep_w[b0:b1], "composite": bool(composite)}
+        if joint and overlap:     # the group's windows as one canvas (a group of one has no seam to fuse)
+            kw["seam_overlap"] = int(overlap)
         if map_w is not None:
             kw["style_map"] = map_w[b0:b1]
         if not guided:
@@ -291,6 +313,10 @@ def parse_args(argv=None):
                    help="ramp every kept region linearly over its N outermost frames (bins)")
     p.add_argument("--no-composite", action="store_false", dest="composite",
                    help="do not paste the content back over the kept region of the decoded windows")
+    p.add_argument("--joint", action="store_true",
+                   help="denoise the windows of a model call as one latent canvas (needs --solver and an --overlap "
+                        "that is a multiple of 8): the columns neighbouring windows share are fused after every step; "
+                        "--batch at least the window count gives one coherent canvas")
     p.add_argument("--batch", type=int, default=8, help="windows per model call")
     p.add_argument("--seed", type=int, default=0)
     args = p.parse_args(argv)
@@ -308,6 +334,10 @@ def parse_args(argv=None):
         p.error("--keep-time / --keep-band need --solver")
     if args.keep_feather < 0:
         p.error("--keep-feather must not be negative")
+    if args.joint and args.solver is None:
+        p.error("--joint needs --solver")
+    if args.joint and args.overlap % 8:
+        p.error("--joint needs an --overlap that is a multiple of 8 (whole latent columns)")
     if len(args.style) == 1:
         args.style = args.style[0]      # a single file: the string it always was
     return args
@@ -335,6 +365,8 @@ def main(argv=None):
         guide["composite"] = args.composite
     if args.style_morph:
         guide["style_map"] = longform.morph_map(len(styles), 1 + content.numel() // HOP)
+    if args.joint:
+        guide["joint"] = True
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
                              num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
                              solver=args.solver, t_start=args.t_start, style_weights=args.style_weights,
