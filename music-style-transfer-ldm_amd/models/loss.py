@@ -95,6 +95,8 @@ def perceptual_loss(original, reconstructed, feature_extractor_type: str = "vggi
     return perceptual_loss_old(original, reconstructed)
 
 
+# The HIP wrappers below (HF.kl_loss / HF.mse_loss and their backward), like the other scalar train-path kernels, are
+# swept against float64 in tests/test_gpu_train_ops.py.
 def kl_regularization_loss(latent):
     """mean(0.5 * (z^2 - 1 - log(z^2 + 1e-8)))  (reference loss.py:31-32)"""
     return HF.kl_loss(latent)
