@@ -131,11 +131,11 @@ static bool use_bneck_fold(const ldm_unet_shape& s, const ldm_unet_weights* w) {
 // token count, which is every caller but a style mix.  Only the K/V projections and the folded keys scale.
 // Invariant of the reverse loop's two phases (sample_prepare / sample_run): every region is a range of its own (take()
 // never hands out overlapping ranges), and the regions the prepare phase fills (kv2, kv1, kf2, bf2, kf1, bf1, ubn,
-// s5cat, s6cat, kb5cat, kb6cat, and the time embeddings behind the carve) are written by no launch of the run phase,
-// which writes z1 .. eps, q*, a*, c*, xs, p1, eb, the keep region behind the time embeddings and the two scratch
-// regions.  Those two, convws and uks, are shared by both phases' launches (the K/V projections' split-K partials, the
-// loop's) but carry nothing from one launch to the next beyond counters that are zero between launches.  A region
-// added for prepared data must keep to this: a range of its own that the loop does not write.
+// s5cat, s6cat, kb5cat, kb6cat, and behind the carve carve_sample's temb_all and temb_b) are written by no launch of
+// the run phase, which writes z1 .. eps, q*, a*, c*, xs, p1, eb, carve_sample's keep region (kbase .. krows) and the two
+// scratch regions.  Those two, convws and uks, are shared by both phases' launches (the K/V projections' split-K
+// partials, the loop's) but carry nothing from one launch to the next beyond counters that are zero between launches.
+// A region added for prepared data must keep to this: a range of its own that the loop does not write.
 static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float* base, int64_t S5 = 0, int64_t S6 = 0,
                     bool guided = false) {
     const int64_t B = s.B, nf = s.nf, HW = (int64_t)s.H * s.W;
@@ -185,6 +185,36 @@ static UNetWs carve(const ldm_unet_shape& s, const ldm_unet_weights* wts, float*
         w.kb6cat = take(B * S6);
     }
     w.total = off;
+    return w;
+}
+
+// The whole workspace of a reverse loop (ldm_sample_workspace_floats): the carve at the shape the body runs at and,
+// behind it, unrounded and in this order, the regions below.  The one statement of that tail's layout.
+struct SampleWs {
+    ldm_unet_shape sh;   // the shape the body runs at: the caller's, guided at twice its batch (targets, then bases)
+    UNetWs ws;
+    // prepare phase: every step's time embeddings [nsteps * sh.B, 128]; guided, the caller's rows [nsteps * B, 128]
+    float *temb_all, *temb_b;   // staged in temb_b before they are doubled into temb_all
+    // run phase, only with the keep: the step kernels' keep region [e_b (guided)] [z0] [n0] [w] [rows].  kbase is its
+    // start (e_b when guided, else z0); z0 / n0 in the state's NHWC layout; krows [nsteps, krl] = {a, b, scale[B] (guided)}
+    float *kbase, *kz0, *kn0, *kw, *krows;
+    int64_t krl, total;
+};
+static SampleWs carve_sample(const ldm_unet_shape& sc, const ldm_unet_weights* wts, float* base, int64_t S5, int64_t S6,
+                             int64_t nsteps, bool guided, bool keep) {
+    SampleWs w{};
+    w.sh = sc, w.sh.B = guided ? 2 * sc.B : sc.B;
+    w.ws = carve(w.sh, wts, base, S5, S6, guided);
+    w.total = w.ws.total;
+    auto take = [&](int64_t n) { return w.total += n, base ? base + (w.total - n) : nullptr; };
+    const int64_t HW = (int64_t)sc.H * sc.W, dense = sc.B * sc.C * HW;
+    w.temb_all = take(nsteps * w.sh.B * 128);
+    w.temb_b = take(guided ? nsteps * sc.B * 128 : 0);
+    w.krl = 2 + (guided ? sc.B : 0);
+    if (keep) {
+        w.kbase = take(guided ? dense : 0), w.kz0 = take(dense), w.kn0 = take(dense);
+        w.kw = take(sc.B * HW), w.krows = take(nsteps * w.krl);
+    }
     return w;
 }
 
@@ -511,15 +541,10 @@ struct Guide {
 // The regional keep (k != NULL): after every step's update the state is blended with the content's
 // own noising trajectory coef[i][0] z0 + coef[i][1] n0 under the keep weights w [B, H, W] (keep_blend); the logs and
 // the 2M history stay the model's prediction.  Only dec1's epilogue differs.  The step kernels read z0 / n0 in the
-// state's NHWC layout from a keep region behind the time embeddings (keep_region_floats), filled once per loop.
+// state's NHWC layout from a keep region behind the time embeddings (carve_sample), filled once per loop.
 struct Keep {
     const float *z0, *n0, *w, *coef;
 };
-// [e_b (guided)] [z0] [n0] [w] [nsteps rows {a, b, scale[B] (guided)}]
-static int64_t keep_region_floats(const ldm_unet_shape& s, int32_t nsteps, bool guided) {
-    const int64_t HW = (int64_t)s.H * s.W, dense = s.B * s.C * HW;
-    return (guided ? 3 : 2) * dense + s.B * HW + (int64_t)nsteps * (2 + (guided ? s.B : 0));
-}
 // rows[i] = {coef[i][0], coef[i][1], scale[0 .. B)} (scale NULL: rows of two)
 __global__ __launch_bounds__(256) void keep_rows_kernel(const float* __restrict__ coef, const float* __restrict__ scale,
                                                         float* __restrict__ rows, int B, int64_t n) {
@@ -551,22 +576,17 @@ static int concat_halves(const float* a, const float* b, float* out, int64_t row
 // workspace's regions and which forms apply.  loop_plan makes the checks that do not depend on the phase, so that
 // the prepare and the run refuse the same arguments.
 struct LoopPlan {
-    ldm_unet_shape sh;    // the shape the body runs at (guided: twice the caller's batch)
     int S5, S6;           // key counts of CA2 / CA1
     bool kb5, kb6;        // a key bias reaches the folded keys (guided: the target's or the base's)
     bool bfold;           // the bottleneck runs on CA1's folded values
     bool map;             // a style map: each step's two attentions read the reference biases (run phase only)
     RefBias rb;
-    UNetWs ws;
-    float* temb_all;      // [nsteps*B, 128] behind the carve (ldm_sample_workspace_floats)
+    SampleWs sw;          // the workspace's regions and the shape the body runs at
     int64_t dense;        // one step of the logs: the caller's batch
 };
 static int loop_plan(const ldm_unet_shape* sc, const ldm_unet_weights* w, const ldm_sample_args& a, const Guide* g,
-                     LoopPlan& lp) {
-    lp.sh = *sc;
-    if (g) lp.sh.B = 2 * sc->B;
-    const ldm_unet_shape* s = &lp.sh;
-    const int L2 = s->H * s->W / 16, L1 = s->H * s->W / 64;
+                     bool keep, LoopPlan& lp) {
+    const int L2 = sc->H * sc->W / 16, L1 = sc->H * sc->W / 64;
     lp.S5 = a.S5 <= 0 ? L2 : a.S5;
     lp.S6 = a.S6 <= 0 ? L1 : a.S6;
     lp.kb5 = a.key_bias5 || (g && g->key_bias5_base);
@@ -582,21 +602,19 @@ static int loop_plan(const ldm_unet_shape* sc, const ldm_unet_weights* w, const 
         LDM_REQUIRE((int64_t)a.refs * L2 == lp.S5 && (int64_t)a.refs * L1 == lp.S6,
                     "style map: S5 / S6 must be refs times the maps' own token counts");
     }
-    lp.ws = carve(*s, w, a.workspace, lp.S5, lp.S6, g != nullptr);
-    lp.temb_all = a.workspace + lp.ws.total;
-    lp.dense = (int64_t)sc->B * s->C * s->H * s->W;
+    lp.sw = carve_sample(*sc, w, a.workspace, lp.S5, lp.S6, a.nsteps, g != nullptr, keep);
+    lp.dense = (int64_t)sc->B * sc->C * sc->H * sc->W;
     LDM_REQUIRE(a.log_step_stride == 0 || a.log_step_stride >= lp.dense, "ddim_sample: log stride smaller than a step");
-    lp.bfold = false;
     if (w->use_fold) {
         LDM_REQUIRE(w->ca_wq_raw[0] && w->ca_wq_raw[1] && w->fold_w[0] && w->fold_w[1] && w->fold_pb[0] && w->fold_pb[1],
                     "ddim_sample: use_fold needs the folded weights");
         if (w->use_step) {
-            LDM_REQUIRE(s->C == 32 && s->nf == 64, "ddim_sample: the step kernels are built for latent 32 / 64 filters");
+            LDM_REQUIRE(sc->C == 32 && sc->nf == 64, "ddim_sample: the step kernels are built for latent 32 / 64 filters");
             for (int l = 0; l < 9; ++l) LDM_REQUIRE(w->step_w[l], "ddim_sample: use_step needs the step weights");
             LDM_REQUIRE(w->step_pb[0] && w->step_pb[1], "ddim_sample: use_step needs the folded biases");
             LDM_REQUIRE(w->step_dtype >= LDM_DT_F32 && w->step_dtype <= LDM_DT_BF16, "ddim_sample: step_dtype");
             // the bottleneck's value fold is built for CA1's own 16 keys without a bias: a mix leaves it
-            lp.bfold = use_bneck_fold(*s, w) && lp.S6 == L1 && !lp.kb6 && !lp.map;   // (nor does a style map)
+            lp.bfold = use_bneck_fold(lp.sw.sh, w) && lp.S6 == L1 && !lp.kb6 && !lp.map;   // (nor does a style map)
         }
     }
     return 0;
@@ -608,20 +626,18 @@ static int loop_plan(const ldm_unet_shape* sc, const ldm_unet_weights* w, const 
 // kv2 / kv1, kf* / bf* and ubn, which the run phase only reads (the invariant stated on carve).
 static int sample_prepare(const ldm_unet_shape* sc, const ldm_unet_weights* w, const ldm_sample_args& a, const Guide* g,
                           const LoopPlan& lp) {
-    const ldm_unet_shape* s = &lp.sh;
-    const UNetWs& ws = lp.ws;
+    const ldm_unet_shape* s = &lp.sw.sh;
+    const UNetWs& ws = lp.sw.ws;
     const int L2 = s->H * s->W / 16, L1 = s->H * s->W / 64;
     const int32_t nsteps = a.nsteps, S5 = lp.S5, S6 = lp.S6;
-    const int64_t* t_table = a.t_table;
     const float *s5 = a.s5, *s6 = a.s6, *key_bias5 = a.key_bias5, *key_bias6 = a.key_bias6;
-    float* temb_all = lp.temb_all;
+    float *temb_all = lp.sw.temb_all, *temb_b = lp.sw.temb_b;
     hipStream_t st = (hipStream_t)a.stream;
     // The time MLP depends only on t: all nsteps*B embeddings in one launch before the loop (the same
     // evaluations the reference makes one step at a time, model.py:203).
+    LDM_TRY(ldm_time_mlp_forward(a.t_table, 0, nsteps * sc->B, 128, w->t_freqs, w->t_w1, w->t_b1, w->t_w2, w->t_b2,
+                                 g ? temb_b : temb_all, st));
     if (g) {   // both halves share t: the caller's [nsteps, B] rows, each repeated for the base half
-        float* temb_b = temb_all + (size_t)nsteps * s->B * 128;
-        LDM_TRY(ldm_time_mlp_forward(t_table, 0, nsteps * sc->B, 128, w->t_freqs, w->t_w1, w->t_b1, w->t_w2, w->t_b2,
-                                     temb_b, st));
         LDM_TRY(concat_halves(temb_b, temb_b, temb_all, nsteps, (int64_t)sc->B * 128, st));
         // the doubled batch's style maps and key biases: targets, then bases
         LDM_TRY(concat_halves(s5, g->s5_base, ws.s5cat, 1, (int64_t)sc->B * 256 * S5, st));
@@ -635,9 +651,6 @@ static int sample_prepare(const ldm_unet_shape* sc, const ldm_unet_weights* w, c
             LDM_TRY(concat_halves(key_bias6, g->key_bias6_base, ws.kb6cat, 1, (int64_t)sc->B * S6, st));
             key_bias6 = ws.kb6cat;
         }
-    } else {
-        LDM_TRY(ldm_time_mlp_forward(t_table, 0, nsteps * s->B, 128, w->t_freqs, w->t_w1, w->t_b1, w->t_w2, w->t_b2,
-                                     temb_all, st));
     }
     // Likewise the style maps' K/V projections (model.py:153 with kv = s5 / s6, fixed for the loop).
     if (S5 == L2 && S6 == L1) {
@@ -660,14 +673,14 @@ static int sample_prepare(const ldm_unet_shape* sc, const ldm_unet_weights* w, c
 // sample_prepare has filled for the same shape, weights and arguments.  It writes none of the prepared regions.
 static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const ldm_sample_args& a, const Guide* g,
                       const Keep* kp, const LoopPlan& lp) {
-    const ldm_unet_shape* s = &lp.sh;
-    const UNetWs& ws = lp.ws;
+    const ldm_unet_shape* s = &lp.sw.sh;
+    const SampleWs& sw = lp.sw;
+    const UNetWs& ws = sw.ws;
     const bool msolver = a.solver == LDM_SOLVER_MULTISTEP;
     const int32_t nsteps = a.nsteps, S5 = lp.S5, S6 = lp.S6;
     const float eta = msolver ? 0.f : a.eta;
-    float *x = a.x, *x0_logs = a.x0_logs, *eps_logs = a.eps_logs, *temb_all = lp.temb_all;
+    float *x = a.x, *x0_logs = a.x0_logs, *eps_logs = a.eps_logs, *temb_all = sw.temb_all;
     const float* coef_table = a.coef_table;
-    const int64_t* t_table = a.t_table;
     // the literal loop's unet_forward names the maps, but with kv_ready it reads only their prepared projections
     const float *s5 = g ? ws.s5cat : a.s5, *s6 = g ? ws.s6cat : a.s6;
     const int64_t dense = lp.dense, n = a.log_step_stride ? a.log_step_stride : dense;
@@ -691,30 +704,25 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
         return fuse;
     };
     if (w->use_fold && w->use_step) {
-        const bool bfold = lp.bfold;
         LDM_TRY(step_layout(x, ws.xs, sc->B, s->C, HW, true, st));
         if (g) LDM_TRY(step_layout(x, ws.xs + dense, sc->B, s->C, HW, true, st));
-        float* kreg = temb_all + (size_t)nsteps * (g ? 3 : 1) * sc->B * 128;   // the keep region
-        const int krl = 2 + (g ? sc->B : 0);
-        float* krows = kreg + (g ? 3 : 2) * dense + (int64_t)sc->B * HW;
-        if (kp) {
-            float* kz = kreg + (g ? dense : 0);
-            LDM_TRY(step_layout(kp->z0, kz, sc->B, s->C, HW, true, st));
-            LDM_TRY(step_layout(kp->n0, kz + dense, sc->B, s->C, HW, true, st));
-            LDM_HIP_TRY(hipMemcpyAsync(kz + 2 * dense, kp->w, (size_t)sc->B * HW * 4, hipMemcpyDeviceToDevice, st));
-            const int64_t nr = (int64_t)nsteps * krl;
+        if (kp) {   // the keep region
+            LDM_TRY(step_layout(kp->z0, sw.kz0, sc->B, s->C, HW, true, st));
+            LDM_TRY(step_layout(kp->n0, sw.kn0, sc->B, s->C, HW, true, st));
+            LDM_HIP_TRY(hipMemcpyAsync(sw.kw, kp->w, (size_t)sc->B * HW * 4, hipMemcpyDeviceToDevice, st));
+            const int64_t nr = (int64_t)nsteps * sw.krl;
             hipLaunchKernelGGL(keep_rows_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, kp->coef,
-                               g ? g->scale : nullptr, krows, sc->B, nr);
+                               g ? g->scale : nullptr, sw.krows, sc->B, nr);
             LDM_CHECK_LAUNCH("keep_rows_kernel");
         }
         LDM_TRY(fuse_seams(ws.xs, true));
         for (int i = 0; i < nsteps; ++i) {
             DdimFuse fuse = make_fuse(i, ws.xs);
             if (kp) {
-                fuse.kbase = kreg, fuse.krow = krows + (size_t)i * krl, fuse.kstride = dense;
-                if (g) fuse.eb = kreg;   // e_b leads the keep region
+                fuse.kbase = sw.kbase, fuse.krow = sw.krows + (size_t)i * sw.krl, fuse.kstride = dense;
+                if (g) fuse.eb = sw.kbase;   // e_b leads the keep region
             }
-            LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, bfold, rb));
+            LDM_TRY(unet_step_kernels(*s, *w, ws, st, temb_all + (size_t)i * s->B * 128, fuse, S5, S6, lp.bfold, rb));
             LDM_TRY(fuse_seams(ws.xs, true));
         }
         return step_layout(ws.xs, x, sc->B, s->C, HW, false, st);
@@ -734,7 +742,7 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
         if (w->use_fold)
             LDM_TRY(unet_forward_folded(*s, *w, xstate, ws, st, temb_all + (size_t)i * s->B * 128, &fuse, S5, S6, rb));
         else
-            LDM_TRY(unet_forward(*s, *w, xstate, t_table + (size_t)i * sc->B, 0, s5, s6, nullptr, ws, st,
+            LDM_TRY(unet_forward(*s, *w, xstate, a.t_table + (size_t)i * sc->B, 0, s5, s6, nullptr, ws, st,
                                  temb_all + (size_t)i * s->B * 128, &fuse, /*kv_ready=*/true));
         LDM_TRY(fuse_seams(xstate, false));
     }
@@ -747,15 +755,9 @@ static int sample_run(const ldm_unet_shape* sc, const ldm_unet_weights* w, const
 static bool guidance_on(const ldm_sample_args& a) { return a.s5_base || a.s6_base || a.guide_scale; }
 static bool keep_on(const ldm_sample_args& a) { return a.z0 || a.n0 || a.keep || a.keep_coef; }
 
-// The unguided carve at the caller's batch, or the guided one at twice it; then the time embeddings of every step
-// (guided: the doubled rows behind the caller's) and, with the keep, its region.
 extern "C" int64_t ldm_sample_workspace_floats(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a) {
     if (!s || !a || a->nsteps < 0 || a->S5 < 0 || a->S6 < 0 || s->B <= 0) return -1;
-    const bool guided = guidance_on(*a);
-    ldm_unet_shape sh = *s;
-    if (guided) sh.B = 2 * s->B;
-    const int64_t n = carve(sh, w, nullptr, a->S5, a->S6, guided).total + (int64_t)a->nsteps * (guided ? 3 : 1) * s->B * 128;
-    return keep_on(*a) ? n + keep_region_floats(*s, a->nsteps, guided) : n;
+    return carve_sample(*s, w, nullptr, a->S5, a->S6, a->nsteps, guidance_on(*a), keep_on(*a)).total;
 }
 
 // The two scratch regions that hold split-K counters and must be zero before a launch: convws at the carve's start
@@ -763,15 +765,12 @@ extern "C" int64_t ldm_sample_workspace_floats(const ldm_unet_shape* s, const ld
 extern "C" int ldm_sample_workspace_zeroed(const ldm_unet_shape* s, const ldm_unet_weights* w, const ldm_sample_args* a,
                                            int64_t* ranges) {
     LDM_REQUIRE(s && a && ranges && a->S5 >= 0 && a->S6 >= 0 && s->B > 0, "sample_workspace_zeroed: bad argument");
-    const bool guided = guidance_on(*a);
-    ldm_unet_shape sh = *s;
-    if (guided) sh.B = 2 * s->B;
     float* const base = reinterpret_cast<float*>(uintptr_t(256));   // (only differences of the carved pointers are read)
-    const UNetWs ws = carve(sh, w, base, a->S5, a->S6, guided);
-    ranges[0] = ws.convws - base;
+    const SampleWs sw = carve_sample(*s, w, base, a->S5, a->S6, 0, guidance_on(*a), false);
+    ranges[0] = sw.ws.convws - base;
     ranges[1] = conv_ws_floats(w);
-    ranges[2] = ws.uks - base;
-    ranges[3] = w && w->use_step ? step_ws_floats(sh.B, sh.H, sh.W) : 0;
+    ranges[2] = sw.ws.uks - base;
+    ranges[3] = w && w->use_step ? step_ws_floats(sw.sh.B, sw.sh.H, sw.sh.W) : 0;
     return 0;
 }
 
@@ -837,8 +836,8 @@ static int sample_phases(const ldm_unet_shape* s, const ldm_unet_weights* w, con
     const Guide g{a->s5_base, a->s6_base, a->key_bias5_base, a->key_bias6_base, a->guide_scale};
     const Keep k{a->z0, a->n0, a->keep, a->keep_coef};
     const Guide* gp = guidance_on(*a) ? &g : nullptr;
-    LoopPlan lp;
-    LDM_TRY(loop_plan(s, w, *a, gp, lp));
+    LoopPlan lp{};
+    LDM_TRY(loop_plan(s, w, *a, gp, keep_on(*a), lp));
     if (phases & PHASE_PREPARE) LDM_TRY(sample_prepare(s, w, *a, gp, lp));
     if (phases & PHASE_RUN) LDM_TRY(sample_run(s, w, *a, gp, keep_on(*a) ? &k : nullptr, lp));
     return 0;

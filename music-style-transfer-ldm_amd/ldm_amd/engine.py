@@ -220,19 +220,23 @@ class UNetEngine:
         plan_batch as in _guided_weights).
         keep: with the regional keep's region.
         One buffer per configuration (ldm_sample_workspace_floats of it) and slot."""
-        own = ((shape.H // 4) * (shape.W // 4), (shape.H // 8) * (shape.W // 8))
-        keys = tuple(0 if int(k) == o else int(k) for k, o in zip(keys, own)) if keys else (0, 0)
-        plan_batch = (plan_batch or 0) if guided else 0
+        keys = keys or (0, 0)
+        # no operands here: a set flag stands for its option's pointers (the size function reads only whether they are set)
+        a = L.SampleArgs(nsteps=int(nsteps), S5=int(keys[0]), S6=int(keys[1]), guide_scale=int(bool(guided)),
+                         keep=int(bool(keep)))
         w = self._guided_weights(shape.B, shape.C, shape.H, shape.W, plan_batch) if guided else self.weights(shape)
-        a = L.SampleArgs(nsteps=int(nsteps), S5=keys[0], S6=keys[1])
-        if guided:   # (the size function reads only whether an option's pointers are set)
-            a.s5_base = a.s6_base = a.guide_scale = 1
-        if keep:
-            a.z0 = a.n0 = a.keep = a.keep_coef = 1
+        return self._workspace(shape, w, a, device, slot, plan_batch)
+
+    def _workspace(self, shape, w, a, device, slot, plan_batch):
+        """The workspace of the call that passes the argument struct `a` (LoopOptions.fill) with the weights w."""
+        own = ((shape.H // 4) * (shape.W // 4), (shape.H // 8) * (shape.W // 8))
+        keys = tuple(0 if k == o else k for k, o in zip((a.S5, a.S6), own))
+        guided, keep = bool(a.s5_base or a.guide_scale), bool(a.z0 or a.keep)
         n = L.load().ldm_sample_workspace_floats(byref(shape), byref(w), byref(a))
         if n <= 0:
             raise RuntimeError("ldm_sample_workspace_floats failed")
-        key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot, keys, bool(guided), plan_batch, bool(keep))
+        key = (shape.B, shape.C, shape.H, shape.W, shape.nf, str(device), slot, keys, guided,
+               (plan_batch or 0) if guided else 0, keep)
         ws = self._ws.get(key)
         if ws is None or ws.numel() < n:
             ws = torch.zeros(int(n), device=device, dtype=torch.float32)
@@ -299,30 +303,6 @@ class UNetEngine:
             return None
         return S5, S6
 
-    def _mix_check(self, x, s5, s6, key_bias5, key_bias6):
-        """Validates a style mix's operands and returns (S5, S6, bias pointers); raises where no mixing path exists."""
-        B, C, H, W = x.shape
-        S5, S6 = s5.shape[2] * s5.shape[3], s6.shape[2] * s6.shape[3]   # (= mix_keys where that is not None)
-        L2, L1 = (H // 4) * (W // 4), (H // 8) * (W // 8)
-        if tuple(s5.shape[:2]) != (B, 256) or tuple(s6.shape[:2]) != (B, 512) or S5 % L2 or S6 % L1 or \
-                S5 // L2 != S6 // L1 or s5.shape[3] != W // 4 or s6.shape[3] != W // 8:
-            raise RuntimeError(f"style mix: style maps must be s5 [B,256,R*H/4,W/4], s6 [B,512,R*H/8,W/8] with one R for "
-                               f"z {tuple(x.shape)}; got {tuple(s5.shape)}, {tuple(s6.shape)}")
-        if not (self.fold and self.fold_applies(self.shape(B, C, H, W))):
-            raise RuntimeError("style mix: several style references need the folded cross-attentions (fold=True, "
-                               "latent planes up to 1024 positions); the unfolded engine has no kernel for them")
-        ptrs = []
-        for kb, S, name in ((key_bias5, S5, "key_bias5"), (key_bias6, S6, "key_bias6")):
-            if kb is None:
-                ptrs.append(None)
-                continue
-            ops.require_device(kb, what=name)
-            if kb.dtype != torch.float32 or tuple(kb.shape) != (B, S) or not kb.is_contiguous():
-                raise RuntimeError(f"style mix: {name} must be a contiguous fp32 [{B},{S}] tensor, got "
-                                   f"{kb.dtype} {tuple(kb.shape)}")
-            ptrs.append(kb.data_ptr())
-        return S5, S6, ptrs[0], ptrs[1]
-
     @staticmethod
     def map_refs(x, s5, s6):
         """R of stacked style maps (s5 [B,256,R*H/4,W/4]): the reference count a style map's biases must have."""
@@ -345,15 +325,6 @@ class UNetEngine:
                 raise ValueError(f"style map: {name} must be a contiguous fp32 [{B},{Lq},{R}] tensor (one log-weight per "
                                  f"sample, query position and reference), got {rb.dtype} {tuple(rb.shape)}")
         ops.require_device(ref_bias5, ref_bias6, what="style map bias")
-
-    def _map_check(self, x, s5, s6, ref_bias5, ref_bias6):
-        """A style map's operands checked against the loop's (no device work).  Returns (R, S5, S6, pointers)."""
-        if ref_bias5 is None or ref_bias6 is None:
-            raise ValueError("style map: ref_bias5 and ref_bias6 go together (one is None)")
-        S5, S6, _, _ = self._mix_check(x, s5, s6, None, None)    # stacked maps of one R, the folded engine
-        R = self.map_refs(x, s5, s6)
-        self.map_layout_check(tuple(x.shape), R, ref_bias5, ref_bias6)
-        return R, S5, S6, ref_bias5.data_ptr(), ref_bias6.data_ptr()
 
     @staticmethod
     def map_values_check(ref_bias5, ref_bias6):
@@ -389,12 +360,6 @@ class UNetEngine:
         if isinstance(guidance_scale, torch.Tensor):
             return bool((guidance_scale.detach() == 1).all())
         return float(guidance_scale) == 1.0
-
-    def _guided_keys(self, x, s5, s6, key_bias5, key_bias6, base):
-        """(S5, S6) of a guided loop: the key counts where either side is a mix (stacked maps or a bias), else (0, 0)."""
-        if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is None and base[2] is None and base[3] is None:
-            return 0, 0
-        return s5.shape[2] * s5.shape[3], s6.shape[2] * s6.shape[3]
 
     def _guided_weights(self, B, C, H, W, plan_batch=None):
         """The weights a guided loop of caller batch B binds: those of the doubled batch 2B the body runs at.
@@ -442,29 +407,6 @@ class UNetEngine:
             raise ValueError("keep: w must lie in [0, 1]")
         return cls.KeepOperands(v.detach().to(device, torch.float32).contiguous() for v in (z0, n0, wf, coefs))
 
-    def _guided_operands(self, x, s5, s6, key_bias5, key_bias6, base, scale):
-        """The guided loop's operands checked: its SampleArgs fields (the key counts, and the biases, the base maps and
-        the scale as pointers)."""
-        B, C, H, W = x.shape
-        s5b, s6b, kb5b, kb6b = base
-        ops.require_device(s5b, s6b, scale, what="guidance operand")
-        if tuple(s5b.shape) != tuple(s5.shape) or tuple(s6b.shape) != tuple(s6.shape):
-            raise ValueError(f"guidance: the base style maps must have the target's shapes (same key counts): target "
-                             f"{tuple(s5.shape)}, {tuple(s6.shape)}; base {tuple(s5b.shape)}, {tuple(s6b.shape)} "
-                             "(LDM.tile_embedding repeats a single style for a mix of R references)")
-        if scale.dtype != torch.float32 or tuple(scale.shape) != (B,) or not scale.is_contiguous():
-            raise ValueError(f"guidance: scale must be a contiguous fp32 [{B}] device tensor, got {scale.dtype} "
-                             f"{tuple(scale.shape)}")
-        S5, S6 = self._guided_keys(x, s5, s6, key_bias5, key_bias6, base)
-        p5 = p6 = p5b = p6b = None
-        if S5:
-            S5, S6, p5, p6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
-            _, _, p5b, p6b = self._mix_check(x, s5b, s6b, kb5b, kb6b)
-        else:
-            self._single_maps_check(x, s5, s6)
-        return dict(S5=S5, S6=S6, key_bias5=p5, key_bias6=p6, s5_base=s5b.data_ptr(), s6_base=s6b.data_ptr(),
-                    key_bias5_base=p5b, key_bias6_base=p6b, guide_scale=scale.data_ptr())
-
     @staticmethod
     def seam_check(seam_cols, W):
         """The joint loop's seam width as an int: 0 (off) or latent columns in [1, W / 2].  ValueError otherwise."""
@@ -473,55 +415,6 @@ class UNetEngine:
             raise ValueError(f"seam_cols must be a whole number of latent columns in [0, W / 2] = [0, {int(W) // 2}], "
                              f"got {seam_cols!r}")
         return ov
-
-    @staticmethod
-    def _single_maps_check(x, s5, s6):
-        B, C, H, W = x.shape
-        if tuple(s5.shape) != (B, 256, H // 4, W // 4) or tuple(s6.shape) != (B, 512, H // 8, W // 8):
-            raise RuntimeError(f"UNet: style maps must be s5 [B,256,H/4,W/4], s6 [B,512,H/8,W/8] for z {tuple(x.shape)}; "
-                               f"got {tuple(s5.shape)}, {tuple(s6.shape)}")
-
-    def _sample_call(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
-                     key_bias5=None, key_bias6=None, base=None, scale=None, plan_batch=None, keep=None, phase=None,
-                     ref_bias5=None, ref_bias6=None, seam_cols=0):
-        """One C loop (ldm_sample) of solver "ddim" / "msolver" on x, with whichever options are given: a mix (stacked
-        s5 / s6, key biases), guidance (base = (s5_base, s6_base, key_bias5_base, key_bias6_base) with the target's key
-        counts, scale a device fp32 [B] tensor (guidance_scale()); plan_batch: see _guided_weights) and the regional
-        keep (keep_operands()).  ref_bias5 / ref_bias6: the style map's biases (ddim_loop); their layout is checked here,
-        their values by the callers (no device work in this function: it runs under capture).  seam_cols: the joint
-        loop's seam width (ddim_loop; checked by seam_check).
-
-        phase None: the whole loop (ldm_sample).  phase "prepare" / "run": that C entry alone (GraphedDDIM, on
-        workspaces of its own: the engine's shared ones are also written by forward() and by captured graphs' replays,
-        so nothing prepared in them is trusted from one call to the next)."""
-        B, C, H, W = x.shape
-        shape = self.shape(B, C, H, W)
-        n = t_table.shape[0]
-        a = L.SampleArgs(solver=L.SOLVER[solver], nsteps=n, eta=float(eta), x=x.data_ptr(), s5=s5.data_ptr(),
-                         s6=s6.data_ptr(), t_table=t_table.data_ptr(), coef_table=coef_table.data_ptr(),
-                         x0_logs=ops._p(x0_logs), eps_logs=ops._p(eps_logs), log_step_stride=int(log_stride),
-                         stream=ops.stream_handle(), seam_cols=self.seam_check(seam_cols, W))
-        if base is not None:
-            for f, v in self._guided_operands(x, s5, s6, key_bias5, key_bias6, base, scale).items():
-                setattr(a, f, v)
-            w = self._guided_weights(B, C, H, W, plan_batch)   # the body runs at the doubled batch: targets, then bases
-        else:
-            if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
-                a.S5, a.S6, a.key_bias5, a.key_bias6 = self._mix_check(x, s5, s6, key_bias5, key_bias6)
-            else:
-                self._single_maps_check(x, s5, s6)
-            w = self.weights(shape)
-        if keep is not None:
-            keep = self.keep_operands(keep, x.shape, n, x.device)
-            a.z0, a.n0, a.keep, a.keep_coef = (v.data_ptr() for v in keep)
-        if ref_bias5 is not None or ref_bias6 is not None:
-            a.refs, S5, S6, a.ref_bias5, a.ref_bias6 = self._map_check(x, s5, s6, ref_bias5, ref_bias6)
-            if not a.S5:    # one reference without a key bias: the maps' own counts, stated
-                a.S5, a.S6 = S5, S6
-        a.workspace = self.workspace(shape, x.device, n, slot, keys=(a.S5, a.S6), guided=base is not None,
-                                     plan_batch=plan_batch, keep=keep is not None).data_ptr()
-        entry = {None: "ldm_sample", "prepare": "ldm_sample_prepare", "run": "ldm_sample_run"}[phase]
-        L.call(entry, byref(shape), byref(w), byref(a))
 
     def msolver_loop(self, x, s5, s6, t_table, coef_table, x0_logs, eps_logs=None, split=1, plan=None, key_bias5=None,
                      key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None, ref_bias6=None,
@@ -535,8 +428,10 @@ class UNetEngine:
         if coef_table.dim() != 2 or coef_table.shape[1] != 8 or coef_table.shape[0] != t_table.shape[0]:
             raise ValueError(f"msolver_loop: coef_table must be [n,8] for n = {t_table.shape[0]} steps, "
                              f"got {tuple(coef_table.shape)}")
-        return self._loop("msolver", x, s5, s6, t_table, coef_table, 0.0, x0_logs, eps_logs, split, plan, key_bias5,
-                          key_bias6, base, guidance_scale, keep, ref_bias5, ref_bias6, seam_cols)
+        opts = LoopOptions(x, t_table.shape[0], s5, s6, key_bias5=key_bias5, key_bias6=key_bias6, base=base,
+                           guidance_scale=guidance_scale, keep=keep, ref_bias5=ref_bias5, ref_bias6=ref_bias6,
+                           seam_cols=seam_cols)
+        return self._loop("msolver", x, opts, t_table, coef_table, 0.0, x0_logs, eps_logs, split, plan)
 
     def ddim_loop(self, x, s5, s6, t_table, coef_table, eta, x0_logs=None, eps_logs=None, split=1, plan=None,
                   key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None,
@@ -579,84 +474,228 @@ class UNetEngine:
         The path is per-sample, so the result is the same up to fp32 summation order (a sub-batch
         size may get a conv plan that splits K differently); the chains' launch and memory latencies
         overlap each other's work."""
-        return self._loop("ddim", x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, split, plan, key_bias5,
-                          key_bias6, base, guidance_scale, keep, ref_bias5, ref_bias6, seam_cols)
+        opts = LoopOptions(x, t_table.shape[0], s5, s6, key_bias5=key_bias5, key_bias6=key_bias6, base=base,
+                           guidance_scale=guidance_scale, keep=keep, ref_bias5=ref_bias5, ref_bias6=ref_bias6,
+                           seam_cols=seam_cols)
+        return self._loop("ddim", x, opts, t_table, coef_table, eta, x0_logs, eps_logs, split, plan)
 
-    def _loop(self, solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, split, plan, key_bias5=None,
-              key_bias6=None, base=None, guidance_scale=1.0, keep=None, ref_bias5=None, ref_bias6=None, seam_cols=0):
-        """The whole batch in one _sample_call, or one per sub-batch chain with every per-sample operand (the maps, the
-        biases, the base, the scales, the keep operands, the logs) sliced with the batch.
+    def _sample_call(self, solver, x, opts, t_table, coef_table, eta, x0_logs, eps_logs, log_stride, slot,
+                     plan_batch=None, phase=None):
+        """One C loop (ldm_sample) of solver "ddim" / "msolver" on x under opts, a checked LoopOptions (or a cut of one)
+        for x's samples.  No checks and no device work here: it runs under capture.  plan_batch: see _guided_weights.
+
+        phase None: the whole loop (ldm_sample).  phase "prepare" / "run": that C entry alone (GraphedDDIM, on
+        workspaces of its own: the engine's shared ones are also written by forward() and by captured graphs' replays,
+        so nothing prepared in them is trusted from one call to the next)."""
+        a = L.SampleArgs(solver=L.SOLVER[solver], nsteps=t_table.shape[0], eta=float(eta), x=x.data_ptr(),
+                         t_table=t_table.data_ptr(), coef_table=coef_table.data_ptr(), x0_logs=ops._p(x0_logs),
+                         eps_logs=ops._p(eps_logs), log_step_stride=int(log_stride), stream=ops.stream_handle())
+        shape, w = self._bind(x, opts, a, slot, plan_batch)
+        entry = {None: "ldm_sample", "prepare": "ldm_sample_prepare", "run": "ldm_sample_run"}[phase]
+        L.call(entry, byref(shape), byref(w), byref(a))
+
+    def _bind(self, x, opts, a, slot, plan_batch):
+        """Fills the SampleArgs a's option fields from opts and its workspace, sized by the very struct the call
+        passes; returns the call's (shape, weights).  Guided, the weights of the doubled batch the body runs at."""
+        B, C, H, W = x.shape
+        shape = self.shape(B, C, H, W)
+        opts.fill(a)
+        w = self._guided_weights(B, C, H, W, plan_batch) if opts.guided else self.weights(shape)
+        a.workspace = self._workspace(shape, w, a, x.device, slot, plan_batch).data_ptr()
+        return shape, w
+
+    def _loop(self, solver, x, opts, t_table, coef_table, eta, x0_logs, eps_logs, split, plan):
+        """The whole batch in one _sample_call, or one per sub-batch chain on that chain's cut of the options and of
+        the logs.  The options are checked once, here, for the whole batch.
         Guided, on the step-kernel path, the chains run the whole batch's plans (_guided_weights), so split > 1 gives
         each sample bitwise what split = 1 gives it while both select the same per-batch forms (the bottleneck value
         fold applies up to a doubled batch of 8)."""
         B, n = x.shape[0], t_table.shape[0]
-        guided = base is not None
-        seam_cols = self.seam_check(seam_cols, x.shape[3])
-        if seam_cols and (split > 1 or (plan and len(plan) > 1)):
+        if opts.seam_cols and (split > 1 or (plan and len(plan) > 1)):
             raise ValueError("seam_cols: the rows of a joint loop are fused across their seams after every step, so the "
                              "batch cannot run as independent sub-batch chains (split > 1 or a multi-chain plan)")
-        if keep is not None:
-            keep = self.keep_operands(keep, x.shape, n, x.device)
-        if ref_bias5 is not None or ref_bias6 is not None:
-            self._map_check(x, s5, s6, ref_bias5, ref_bias6)
-            if not torch.cuda.is_current_stream_capturing():    # (a captured loop's static buffers were checked)
-                self.map_values_check(ref_bias5, ref_bias6)
-        scale = None
-        if guided:
-            if len(base) != 4:
-                raise ValueError("base must be (s5_base, s6_base, key_bias5_base, key_bias6_base)")
-            scale = guidance_scale
-            if not (isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and
-                    tuple(scale.shape) == (B,) and scale.is_contiguous()):   # (a graph's static buffer is passed as it is)
-                scale = self.guidance_scale(scale, B, x.device)
-            base = (ops.f32c(base[0]), ops.f32c(base[1]), base[2], base[3])
-        else:
-            if not self.is_unguided(None, guidance_scale):
-                raise ValueError("guidance_scale other than 1 needs a base style to guide against (base=)")
-            if self.mix_keys(x, s5, s6, key_bias5, key_bias6) is not None:
-                self._mix_check(x, s5, s6, key_bias5, key_bias6)
+        opts.check(self, x, n)
+        if not torch.cuda.is_current_stream_capturing():    # (a captured loop's static buffers were checked)
+            opts.check_values()
         if plan is None:
             plan = self.split_plan(t_table, B, split) if split > 1 else None
         if not plan or len(plan) == 1:
-            self._sample_call(solver, x, s5, s6, t_table, coef_table, eta, x0_logs, eps_logs, 0, 0, key_bias5, key_bias6,
-                              base, scale, None, keep, ref_bias5=ref_bias5, ref_bias6=ref_bias6, seam_cols=seam_cols)
+            self._sample_call(solver, x, opts, t_table, coef_table, eta, x0_logs, eps_logs, 0, 0)
             return x
         per_step = x[0].numel() * B
         main = torch.cuda.current_stream(x.device)
         streams = self.side_streams(x.device, len(plan))
-        C, H, W = x.shape[1:]
-        keys = self._guided_keys(x, s5, s6, key_bias5, key_bias6, base) if guided else \
-            self.mix_keys(x, s5, s6, key_bias5, key_bias6)
-        for k, (lo, hi, t_sub) in enumerate(plan):   # bind / pack / allocate on the main stream first
-            self.workspace(self.shape(hi - lo, C, H, W), x.device, n, k, keys=keys, guided=guided,
-                           plan_batch=B if guided else None, keep=keep is not None)
-
-        def cut(lo, hi):
-            """(x, s5, s6, x0_logs, eps_logs, key_bias5, key_bias6, base, scale, keep) of samples [lo, hi)"""
-            def c(v):
-                return None if v is None else v[lo:hi]
-            return (x[lo:hi], s5[lo:hi], s6[lo:hi], None if x0_logs is None else x0_logs[0, lo:hi],
-                    None if eps_logs is None else eps_logs[0, lo:hi], c(key_bias5), c(key_bias6),
-                    tuple(c(v) for v in base) if guided else None, c(scale), self._keep_cut(keep, lo, hi))
-
-        for k, (lo, hi, t_sub) in enumerate(plan):
-            st = streams[k]
+        plan_batch = B if opts.guided else None
+        chains = [(st, x[lo:hi], opts.cut(lo, hi), t_sub, None if x0_logs is None else x0_logs[0, lo:hi],
+                   None if eps_logs is None else eps_logs[0, lo:hi]) for st, (lo, hi, t_sub) in zip(streams, plan)]
+        for k, (st, xs, oc, t_sub, x0l, epl) in enumerate(chains):   # bind / pack / allocate on the main stream first
+            self._bind(xs, oc, L.SampleArgs(nsteps=n), k, plan_batch)
+        for k, (st, xs, oc, t_sub, x0l, epl) in enumerate(chains):
             st.wait_stream(main)
             if not torch.cuda.is_current_stream_capturing():
                 t_sub.record_stream(st)
             with torch.cuda.stream(st):
-                xs, a5, a6, x0l, epl, b5, b6, gb, gs, kc = cut(lo, hi)
-                c5, c6 = (None if v is None else v[lo:hi] for v in (ref_bias5, ref_bias6))   # the chain's maps
-                self._sample_call(solver, xs, a5, a6, t_sub, coef_table, eta, x0l, epl, per_step, k, b5, b6, gb, gs,
-                                  B if guided else None, kc, ref_bias5=c5, ref_bias6=c6)
+                self._sample_call(solver, xs, oc, t_sub, coef_table, eta, x0l, epl, per_step, k, plan_batch)
         for st in streams:
             main.wait_stream(st)
         return x
 
-    @classmethod
-    def _keep_cut(cls, kp, lo, hi):
-        """A sub-batch chain's slice of the keep operands (the coefficient table is shared)."""
-        return None if kp is None else cls.KeepOperands((kp[0][lo:hi], kp[1][lo:hi], kp[2][lo:hi], kp[3]))
+
+class LoopOptions:
+    """Everything a reverse loop takes besides the state, the tables and the logs (UNetEngine.ddim_loop documents the
+    options): the style maps, the mix's key biases, the guidance base and scale, the regional keep's operands, the style
+    map's reference biases and the joint loop's seam width.  Built from the public arguments, checked once for the whole
+    batch (check), cut per sub-batch chain (cut) and written into the C argument struct (fill)."""
+    # field -> the ldm_sample_args pointer it fills.  Every one is per-sample ([B, ...]) unless listed in SHARED.
+    POINTERS = {"s5": "s5", "s6": "s6", "key_bias5": "key_bias5", "key_bias6": "key_bias6", "ref_bias5": "ref_bias5",
+                "ref_bias6": "ref_bias6", "s5_base": "s5_base", "s6_base": "s6_base", "key_bias5_base": "key_bias5_base",
+                "key_bias6_base": "key_bias6_base", "scale": "guide_scale", "z0": "z0", "n0": "n0", "keep_w": "keep",
+                "keep_coef": "keep_coef"}
+    SHARED = ("keep_coef", "seam_cols", "S5", "S6", "refs")   # cut() carries these over as they are
+    __slots__ = tuple(POINTERS) + ("seam_cols", "S5", "S6", "refs")
+
+    def __init__(self, x, n, s5, s6, key_bias5=None, key_bias6=None, base=None, guidance_scale=1.0, keep=None,
+                 ref_bias5=None, ref_bias6=None, seam_cols=0):
+        """The public arguments of a loop of n steps on x (read for its shape and device), normalised: the maps
+        contiguous fp32, the scale a contiguous fp32 [B] tensor on x's device (a graph's static buffer is taken as it
+        is), the keep as keep_operands() gives it.  ValueError for a bad scale, keep or seam width."""
+        B = x.shape[0]
+        self.s5, self.s6 = ops.f32c(s5), ops.f32c(s6)
+        self.key_bias5, self.key_bias6, self.ref_bias5, self.ref_bias6 = key_bias5, key_bias6, ref_bias5, ref_bias6
+        self.seam_cols = UNetEngine.seam_check(seam_cols, x.shape[3])
+        self.s5_base = self.s6_base = self.key_bias5_base = self.key_bias6_base = self.scale = None
+        if base is not None:
+            if len(base) != 4:
+                raise ValueError("base must be (s5_base, s6_base, key_bias5_base, key_bias6_base)")
+            self.s5_base, self.s6_base, self.key_bias5_base, self.key_bias6_base = \
+                ops.f32c(base[0]), ops.f32c(base[1]), base[2], base[3]
+            sc = guidance_scale
+            if not (isinstance(sc, torch.Tensor) and sc.is_cuda and sc.dtype == torch.float32 and
+                    tuple(sc.shape) == (B,) and sc.is_contiguous()):
+                sc = UNetEngine.guidance_scale(sc, B, x.device)
+            self.scale = sc
+        elif not UNetEngine.is_unguided(None, guidance_scale):
+            raise ValueError("guidance_scale other than 1 needs a base style to guide against (base=)")
+        self.z0, self.n0, self.keep_w, self.keep_coef = \
+            (None,) * 4 if keep is None else UNetEngine.keep_operands(keep, x.shape, n, x.device)
+        self.S5 = self.S6 = self.refs = None     # the key counts and the reference count: check() derives them
+
+    guided = property(lambda self: self.s5_base is not None)
+    mapped = property(lambda self: self.ref_bias5 is not None or self.ref_bias6 is not None)
+
+    def _key_biases(self):
+        return self.key_bias5, self.key_bias6, self.key_bias5_base, self.key_bias6_base
+
+    def is_mix(self, x):
+        """True where the loop on x needs the mixing attention (UNetEngine.mix_keys, or a key bias of the base, or a
+        style map): 4-D maps that are stacked references, or come with a key bias or reference biases."""
+        return self.s5.dim() == 4 and self.s6.dim() == 4 and (
+            self.mapped or any(b is not None for b in self._key_biases()) or
+            UNetEngine.mix_keys(x, self.s5, self.s6) is not None)
+
+    def base_check(self):
+        """ValueError unless the base style maps have the target's shapes (no device work, on any device)."""
+        s5, s6, s5b, s6b = self.s5, self.s6, self.s5_base, self.s6_base
+        if self.guided and (tuple(s5b.shape) != tuple(s5.shape) or tuple(s6b.shape) != tuple(s6.shape)):
+            raise ValueError(f"guidance: the base style maps must have the target's shapes (same key counts): target "
+                             f"{tuple(s5.shape)}, {tuple(s6.shape)}; base {tuple(s5b.shape)}, {tuple(s6b.shape)} "
+                             "(LDM.tile_embedding repeats a single style for a mix of R references)")
+
+    def public(self):
+        """The keyword arguments of UNetEngine.ddim_loop / msolver_loop that give these options again; none for the
+        plain loop, which stays the positional call."""
+        kw = {}
+        if self.guided:
+            kw.update(base=self.prepare_operands()[4:], guidance_scale=self.scale)
+        if self.z0 is not None:
+            kw["keep"] = UNetEngine.KeepOperands((self.z0, self.n0, self.keep_w, self.keep_coef))
+        if self.mapped:
+            kw.update(ref_bias5=self.ref_bias5, ref_bias6=self.ref_bias6)
+        if self.seam_cols:
+            kw["seam_cols"] = self.seam_cols
+        if kw or self.key_bias5 is not None or self.key_bias6 is not None:
+            kw.update(key_bias5=self.key_bias5, key_bias6=self.key_bias6)
+        return kw
+
+    def check(self, engine, x, n):
+        """The operands' layouts against a loop of `engine` on x (no device work; the constructor has checked the keep
+        against n), and the key counts (S5, S6) and reference count they give.  RuntimeError where no kernel exists or
+        an operand is not on the GPU, ValueError for the guidance's and the style map's operands."""
+        B, C, H, W = x.shape
+        L2, L1 = (H // 4) * (W // 4), (H // 8) * (W // 8)
+        s5, s6 = self.s5, self.s6
+        if self.mapped and (self.ref_bias5 is None or self.ref_bias6 is None):
+            raise ValueError("style map: ref_bias5 and ref_bias6 go together (one is None)")
+        self.base_check()
+        if self.guided:
+            ops.require_device(self.s5_base, self.s6_base, self.scale, what="guidance operand")
+            sc = self.scale
+            if sc.dtype != torch.float32 or tuple(sc.shape) != (B,) or not sc.is_contiguous():
+                raise ValueError(f"guidance: scale must be a contiguous fp32 [{B}] device tensor, got {sc.dtype} "
+                                 f"{tuple(sc.shape)}")
+        if not self.is_mix(x):
+            if tuple(s5.shape) != (B, 256, H // 4, W // 4) or tuple(s6.shape) != (B, 512, H // 8, W // 8):
+                raise RuntimeError(f"UNet: style maps must be s5 [B,256,H/4,W/4], s6 [B,512,H/8,W/8] for z "
+                                   f"{tuple(x.shape)}; got {tuple(s5.shape)}, {tuple(s6.shape)}")
+            self.S5 = self.S6 = self.refs = 0      # today's single maps: the maps' own counts
+            return
+        S5, S6 = s5.shape[2] * s5.shape[3], s6.shape[2] * s6.shape[3]
+        if tuple(s5.shape[:2]) != (B, 256) or tuple(s6.shape[:2]) != (B, 512) or S5 % L2 or S6 % L1 or \
+                S5 // L2 != S6 // L1 or s5.shape[3] != W // 4 or s6.shape[3] != W // 8:
+            raise RuntimeError(f"style mix: style maps must be s5 [B,256,R*H/4,W/4], s6 [B,512,R*H/8,W/8] with one R for "
+                               f"z {tuple(x.shape)}; got {tuple(s5.shape)}, {tuple(s6.shape)}")
+        if not (engine.fold and engine.fold_applies(engine.shape(B, C, H, W))):
+            raise RuntimeError("style mix: several style references need the folded cross-attentions (fold=True, "
+                               "latent planes up to 1024 positions); the unfolded engine has no kernel for them")
+        for kb, S, name in zip(self._key_biases(), (S5, S6, S5, S6), ("key_bias5", "key_bias6") * 2):
+            if kb is None:
+                continue
+            ops.require_device(kb, what=name)
+            if kb.dtype != torch.float32 or tuple(kb.shape) != (B, S) or not kb.is_contiguous():
+                raise RuntimeError(f"style mix: {name} must be a contiguous fp32 [{B},{S}] tensor, got "
+                                   f"{kb.dtype} {tuple(kb.shape)}")
+        if self.mapped:
+            UNetEngine.map_layout_check(tuple(x.shape), S5 // L2, self.ref_bias5, self.ref_bias6)
+        self.S5, self.S6, self.refs = S5, S6, (S5 // L2 if self.mapped else 0)
+
+    def check_values(self):
+        """The checks that read device values on the host (skipped under capture): the style map's biases.  The keep
+        weights' range is read where keep_operands() first sees them."""
+        if self.mapped:
+            UNetEngine.map_values_check(self.ref_bias5, self.ref_bias6)
+
+    def _copy(self, per_sample):
+        o = object.__new__(LoopOptions)
+        for f in self.__slots__:
+            v = getattr(self, f)
+            setattr(o, f, v if v is None or f in self.SHARED else per_sample(v))
+        return o
+
+    def cut(self, lo, hi):
+        """The options of samples [lo, hi): every per-sample operand sliced, the SHARED ones carried over.  A cut of a
+        checked record is a checked record."""
+        return self._copy(lambda v: v[lo:hi])
+
+    def clone(self):
+        """The same options on tensors of their own (GraphedDDIM's static buffers; the keep's coefficients included)."""
+        o = self._copy(lambda v: v.contiguous().clone())
+        o.keep_coef = None if self.keep_coef is None else self.keep_coef.clone()
+        return o
+
+    def fill(self, a):
+        """Sets the option fields of the SampleArgs a: the key counts, the reference count, the seam width and every
+        operand's pointer (NULL for an absent one).  Only from a checked record."""
+        if self.S5 is None:
+            raise RuntimeError("LoopOptions.fill: check() the options first (it derives the key counts)")
+        a.S5, a.S6, a.refs, a.seam_cols = self.S5, self.S6, self.refs, self.seam_cols
+        for f, arg in self.POINTERS.items():
+            setattr(a, arg, ops._p(getattr(self, f)))
+
+    def prepare_operands(self):
+        """The tensors the prepare phase reads (GraphedDDIM.replay), None for an absent one: the maps, the key biases
+        and the base.  Not the scale, the keep's operands or the style map: the run phase reads those."""
+        return (self.s5, self.s6, self.key_bias5, self.key_bias6, self.s5_base, self.s6_base, self.key_bias5_base,
+                self.key_bias6_base)
 
 
 class GraphedDDIM:
@@ -678,9 +717,6 @@ class GraphedDDIM:
         seam_cols: joint sampling as in UNetEngine.ddim_loop (the fuses are captured with the loop; not with split > 1)."""
         if solver not in ("ddim", "msolver"):
             raise ValueError(f"GraphedDDIM: unknown solver {solver!r}")
-        self.seam_cols = engine.seam_check(seam_cols, x_init.shape[3])
-        if self.seam_cols and split > 1:
-            raise ValueError("GraphedDDIM: seam_cols needs split = 1 (the rows of a joint loop are not independent)")
         self.solver = solver
         logs = logs or solver == "msolver"
         self.engine = engine
@@ -688,28 +724,17 @@ class GraphedDDIM:
         dev = x_init.device
         self.x_init = x_init.contiguous().clone()
         self.x = torch.empty_like(self.x_init)
-        self.s5 = s5.contiguous().clone()
-        self.s6 = s6.contiguous().clone()
-        self.kb5 = None if key_bias5 is None else key_bias5.contiguous().clone()
-        self.kb6 = None if key_bias6 is None else key_bias6.contiguous().clone()
-        self.rb5 = self.rb6 = None
-        if ref_bias5 is not None or ref_bias6 is not None:
-            engine._map_check(self.x, self.s5, self.s6, ref_bias5, ref_bias6)
-            engine.map_values_check(ref_bias5, ref_bias6)
-            self.rb5, self.rb6 = ref_bias5.clone(), ref_bias6.clone()
-        self.base = self.scale = None
-        if base is not None:
-            self.base = tuple(None if v is None else ops.f32c(v).clone() for v in base)
-            self.scale = engine.guidance_scale(guidance_scale, x_init.shape[0], dev)
-        elif not engine.is_unguided(None, guidance_scale):
-            raise ValueError("guidance_scale other than 1 needs a base style to guide against (base=)")
         self.t_table = t_table.to(dev).contiguous()
         self.coef = coef_table.to(dev).contiguous()
         n = self.t_table.shape[0]
-        self.keep = None
-        if keep is not None:
-            kp = engine.keep_operands(keep, x_init.shape, n, dev)
-            self.keep = engine.KeepOperands(v.clone() for v in kp)
+        opts = LoopOptions(self.x, n, s5, s6, key_bias5=key_bias5, key_bias6=key_bias6, base=base,
+                           guidance_scale=guidance_scale, keep=keep, ref_bias5=ref_bias5, ref_bias6=ref_bias6,
+                           seam_cols=seam_cols)
+        if opts.seam_cols and split > 1:
+            raise ValueError("GraphedDDIM: seam_cols needs split = 1 (the rows of a joint loop are not independent)")
+        opts.check(engine, self.x, n)
+        opts.check_values()
+        self.opts = opts.clone()      # the static buffers of every operand: the captured loops read these
         self.x0_logs = torch.empty((n,) + tuple(x_init.shape), device=dev) if logs else None
         self.eps_logs = torch.empty((n,) + tuple(x_init.shape), device=dev) if logs else None
         self.eta = float(eta)
@@ -728,30 +753,22 @@ class GraphedDDIM:
             return [(0, 0, self.x.shape[0], self.t_table)]
         return [(k, lo, hi, t_sub) for k, (lo, hi, t_sub) in enumerate(self.plan)]
 
+    s5, s6 = property(lambda self: self.opts.s5), property(lambda self: self.opts.s6)
+    kb5, kb6 = property(lambda self: self.opts.key_bias5), property(lambda self: self.opts.key_bias6)
+
     def _chain_call(self, k, lo, hi, t_sub, phase):
         """One phase (ldm_sample_prepare / ldm_sample_run) of chain k on its own workspace."""
-        def c(v):
-            return None if v is None else v[lo:hi]
-        split = bool(self.plan)
-        gb = None if self.base is None else tuple(c(v) for v in self.base)
+        split, B = bool(self.plan), self.x.shape[0]
         x0l = None if self.x0_logs is None else (self.x0_logs[0, lo:hi] if split else self.x0_logs)
         epl = None if self.eps_logs is None else (self.eps_logs[0, lo:hi] if split else self.eps_logs)
-        per_step = self.x[0].numel() * self.x.shape[0] if split else 0
-        self.engine._sample_call(self.solver, self.x[lo:hi], self.s5[lo:hi], self.s6[lo:hi], t_sub, self.coef, self.eta,
-                                 x0l, epl, per_step, self._slot + (k,), c(self.kb5), c(self.kb6), gb, c(self.scale),
-                                 self.x.shape[0] if (split and gb is not None) else None,
-                                 self.engine._keep_cut(self.keep, lo, hi), phase=phase, ref_bias5=c(self.rb5),
-                                 ref_bias6=c(self.rb6), seam_cols=self.seam_cols)
-
-    def _operands(self):
-        """The static tensors the prepare phase reads."""
-        return (self.s5, self.s6, self.kb5, self.kb6) + (self.base if self.base is not None else (None,) * 4) + \
-            (self.t_table,)
+        self.engine._sample_call(self.solver, self.x[lo:hi], self.opts.cut(lo, hi), t_sub, self.coef, self.eta, x0l, epl,
+                                 self.x[0].numel() * B if split else 0, self._slot + (k,),
+                                 B if (split and self.opts.guided) else None, phase)
 
     def prepared_key(self, weight_version=None):
         """prepared_key of the static buffers and the engine's weights as they stand (host only, no device work)."""
         wv = self.engine.weight_version() if weight_version is None else weight_version
-        return prepared_key(self._operands(), wv)
+        return prepared_key(self.opts.prepare_operands() + (self.t_table,), wv)
 
     def _build(self):
         """Warm-up, then two captured graphs per chain: the prepare (style and time state) and the loop.  Run again
@@ -789,29 +806,31 @@ class GraphedDDIM:
     def set_guidance_scale(self, guidance_scale):
         """Writes new strengths (float or [B]) into the static buffer the captured loop reads: the next replay runs
         at them.  Only for a graph captured with a base style."""
-        if self.scale is None:
+        scale = self.opts.scale
+        if scale is None:
             raise ValueError("set_guidance_scale: this loop was captured without a base style")
-        self.scale.copy_(self.engine.guidance_scale(guidance_scale, self.scale.shape[0]), non_blocking=False)
+        scale.copy_(self.engine.guidance_scale(guidance_scale, scale.shape[0]), non_blocking=False)
 
     def set_keep(self, w):
         """Writes new keep weights ([B,H,W] in [0,1]) into the static buffer the captured loop reads: the next replay
         runs under the new mask.  Only for a graph captured with keep=."""
-        if self.keep is None:
+        o = self.opts
+        if o.keep_w is None:
             raise ValueError("set_keep: this loop was captured without keep=")
-        kp = self.engine.keep_operands((self.keep[0], self.keep[1], w, self.keep[3]), self.x.shape, self.keep[3].shape[0],
-                                       self.x.device)
-        self.keep[2].copy_(kp[2], non_blocking=False)
+        kp = self.engine.keep_operands((o.z0, o.n0, w, o.keep_coef), self.x.shape, o.keep_coef.shape[0], self.x.device)
+        o.keep_w.copy_(kp[2], non_blocking=False)
 
     def set_style_map(self, ref_bias5, ref_bias6):
         """Writes a new style map (UNetEngine.ddim_loop's ref_bias5 / ref_bias6) into the static buffers the captured
         loop reads: the next replay runs under it.  No new capture and no prepare launch: the biases are not among the
         prepare phase's operands.  Only for a graph captured with a style map."""
-        if self.rb5 is None:
+        o = self.opts
+        if not o.mapped:
             raise ValueError("set_style_map: this loop was captured without a style map (ref_bias5= / ref_bias6=)")
-        self.engine._map_check(self.x, self.s5, self.s6, ref_bias5, ref_bias6)
+        self.engine.map_layout_check(tuple(self.x.shape), o.refs, ref_bias5, ref_bias6)
         self.engine.map_values_check(ref_bias5, ref_bias6)
-        self.rb5.copy_(ref_bias5, non_blocking=False)
-        self.rb6.copy_(ref_bias6, non_blocking=False)
+        o.ref_bias5.copy_(ref_bias5, non_blocking=False)
+        o.ref_bias6.copy_(ref_bias6, non_blocking=False)
 
     def replay(self):
         """Launches the loop graphs; the prepare graphs first when a static buffer the prepare phase reads (s5, s6,

@@ -38,7 +38,7 @@ from ldm_amd import functional as HF
 from ldm_amd import graphs as hgraphs
 from ldm_amd import nn as hnn
 from ldm_amd import ops
-from ldm_amd.engine import UNetEngine
+from ldm_amd.engine import LoopOptions, UNetEngine
 
 
 # ------------------------------------------------------------------------------------------------
@@ -447,84 +447,58 @@ class LDM(nn.Module):
 
         seam_cols: joint sampling (UNetEngine.ddim_loop): the rows of z_t are neighbouring windows sharing that many
         latent columns, fused before step 0 and after every step.  The engine is called without a split."""
-        seam_cols = UNetEngine.seam_check(seam_cols, z_t.shape[3])
-        guided = not UNetEngine.is_unguided(base_embedding, guidance_scale)
-        if guided:      # the checks, before anything runs
-            if base_embedding is None:
-                raise ValueError("guidance_scale other than 1 needs a base style to guide against (base_embedding=)")
-            scale = UNetEngine.guidance_scale(guidance_scale, z_t.shape[0])      # ValueError on NaN / inf / a wrong count
-            for k in ("s5", "s6"):
-                if tuple(base_embedding[k].shape) != tuple(style_embedding[k].shape):
-                    raise ValueError(
-                        f"guidance: the base embedding must have the target's key counts: target s5 "
-                        f"{tuple(style_embedding['s5'].shape)}, s6 {tuple(style_embedding['s6'].shape)}; base s5 "
-                        f"{tuple(base_embedding['s5'].shape)}, s6 {tuple(base_embedding['s6'].shape)} (tile_embedding "
-                        "repeats a single style for a mix of R references)")
         n = int(times.numel()) - 1
         logs = {"timesteps": [], "pred_x0": [], "noise_pred": []}
-        if keep is not None:
-            keep = UNetEngine.keep_operands(keep, z_t.shape, max(n, 0), z_t.device)   # ValueError on a bad mask
+        dev = z_t.device
+        emb_b = base_embedding
+        # the checks, before anything runs: ValueError on a bad scale, base, mask or seam width
+        opts = LoopOptions(z_t, max(n, 0), style_embedding["s5"], style_embedding["s6"],
+                           key_bias5=style_embedding.get("key_bias5"), key_bias6=style_embedding.get("key_bias6"),
+                           base=emb_b and (emb_b["s5"], emb_b["s6"], emb_b.get("key_bias5"), emb_b.get("key_bias6")),
+                           guidance_scale=guidance_scale, keep=keep, ref_bias5=ref_bias and ref_bias[0].to(dev),
+                           ref_bias6=ref_bias and ref_bias[1].to(dev), seam_cols=seam_cols)
+        opts.base_check()
         if n <= 0:
             return z_t, logs
+        x = ops.f32c(z_t).clone()
         if order:
             coefs = self.noise_scheduler.multistep_coefs(times, order=order)
         else:
             coefs = self.noise_scheduler.reverse_coefs(times)
-        dev = z_t.device
-        x = ops.f32c(z_t).clone()
         B = x.shape[0]
         t_table = times[:-1].view(n, 1).expand(n, B).contiguous().to(dev)
         x0_logs = torch.empty((n,) + tuple(x.shape), device=dev, dtype=torch.float32)
         eps_logs = torch.empty_like(x0_logs)
-        s5 = ops.f32c(style_embedding["s5"])
-        s6 = ops.f32c(style_embedding["s6"])
-        kb5, kb6 = style_embedding.get("key_bias5"), style_embedding.get("key_bias6")
-        mix = UNetEngine.mix_keys(x, s5, s6, kb5, kb6) is not None   # several references (encode_styles)
         coefs = coefs.to(dev)
-        guide = {}
-        if guided:
-            base = (ops.f32c(base_embedding["s5"]), ops.f32c(base_embedding["s6"]), base_embedding.get("key_bias5"),
-                    base_embedding.get("key_bias6"))
-            scale = scale.to(dev)
-            mix = mix or base[2] is not None or base[3] is not None
-            guide = {"base": base, "guidance_scale": scale}
-        if keep is not None:
-            guide["keep"] = keep
-        if ref_bias is not None:
-            mix = True
-            guide.update(ref_bias5=ref_bias[0].to(dev), ref_bias6=ref_bias[1].to(dev))
-        if seam_cols and B > 1:
-            guide["seam_cols"] = seam_cols
-        if mix or guide:    # (the plain call stays the positional one)
-            guide.update(key_bias5=kb5, key_bias6=kb6)
         with torch.no_grad():
             if UNetEngine.supports(x.shape[1]):
                 eng = engine_for(self.unet)
                 if order:
-                    eng.msolver_loop(x, s5, s6, t_table, coefs, x0_logs, eps_logs, **guide)
+                    eng.msolver_loop(x, opts.s5, opts.s6, t_table, coefs, x0_logs, eps_logs, **opts.public())
                 else:
-                    eng.ddim_loop(x, s5, s6, t_table, coefs, float(eta), x0_logs, eps_logs, **guide)
+                    eng.ddim_loop(x, opts.s5, opts.s6, t_table, coefs, float(eta), x0_logs, eps_logs, **opts.public())
             else:   # latent widths the fused engine does not take: per-layer UNet + the update kernel
-                if mix:
+                if opts.is_mix(x):
                     raise RuntimeError(f"style mix: latent width {x.shape[1]} runs the per-layer path, which takes one "
                                        "style map per sample (the fused engine needs a multiple of 8, at least 16)")
-                emb = {"s5": s5, "s6": s6}
-                emb_b = {"s5": base[0], "s6": base[1]} if guided else None
-                if seam_cols and B > 1:     # the stand-alone fuse: before step 0, then after every step
-                    ops.seam_fuse_(x, seam_cols)
+                emb = {"s5": opts.s5, "s6": opts.s6}
+                emb_b = {"s5": opts.s5_base, "s6": opts.s6_base} if opts.guided else None
+                seam = opts.seam_cols if B > 1 else 0
+                if seam:     # the stand-alone fuse: before step 0, then after every step
+                    ops.seam_fuse_(x, seam)
                 for i in range(n):
                     eps = self.unet(x, t_table[i], emb)
-                    if guided:      # the second UNet call of the step, then the guidance kernel
-                        eps = ops.guide_eps(ops.f32c(eps), ops.f32c(self.unet(x, t_table[i], emb_b)), scale)
+                    if opts.guided:      # the second UNet call of the step, then the guidance kernel
+                        eps = ops.guide_eps(ops.f32c(eps), ops.f32c(self.unet(x, t_table[i], emb_b)), opts.scale)
                     if order:
                         ops.msolver_step_(x, eps, coefs[i].contiguous(), x0_logs[i], x0_logs[i - 1] if i else None,
                                           eps_logs[i])
                     else:
                         ops.ddim_step_(x, eps, coefs[i].contiguous(), float(eta), x0_logs[i], eps_logs[i])
-                    if keep is not None:    # the stand-alone blend, after the update kernel
-                        ops.keep_blend_(x, keep[0], keep[1], keep[2], keep[3][i])
-                    if seam_cols and B > 1:
-                        ops.seam_fuse_(x, seam_cols)
+                    if opts.z0 is not None:    # the stand-alone blend, after the update kernel
+                        ops.keep_blend_(x, opts.z0, opts.n0, opts.keep_w, opts.keep_coef[i])
+                    if seam:
+                        ops.seam_fuse_(x, seam)
         logs["timesteps"] = [int(v) for v in times[:-1]]
         logs["pred_x0"] = list(x0_logs.unbind(0))
         logs["noise_pred"] = list(eps_logs.unbind(0))
@@ -709,7 +683,7 @@ class LDM(nn.Module):
             raise ValueError(f"unknown solver {solver!r}: one of {sorted(self._SOLVERS)}")
         rb = None if style_map is None else self._map_biases(style_map, style_embedding, z_t)
         return self._reverse(z_t, style_embedding, times, eta, self._SOLVERS[solver], base_embedding, guidance_scale,
-                             keep, rb, seam_cols)
+                             keep=keep, ref_bias=rb, seam_cols=seam_cols)
 
     @classmethod
     def _seam_cols(cls, seam_overlap, frames, solver):
@@ -771,8 +745,8 @@ class LDM(nn.Module):
         t_start = self.num_timesteps - 1 if t_start is None else t_start
         times = self.sample_times(t_start, steps)
         kp = None if keep is None else self._keep_tuple(keep, z0, noise, times, exact_last)
-        return self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp, style_map,
-                           seam_cols)
+        return self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, keep=kp,
+                           style_map=style_map, seam_cols=seam_cols)
 
     def content_style_transfer(self, content_spec, style_spec, t_start=99, steps=10, solver="dpmpp2m", noise=None,
                                eta=0.0, style_weights=None, guidance_scale=1.0, base_style=None, keep=None,
@@ -859,8 +833,8 @@ class LDM(nn.Module):
             R = int(style_embedding.get("refs", 1)) if isinstance(style_embedding, dict) else 1
             if R > 1:
                 base_embedding = self.tile_embedding(base_embedding, R)
-            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, kp,
-                                     style_map, seam_cols)
+            sampled, _ = self._solve(z_t, style_embedding, times, solver, eta, base_embedding, guidance_scale, keep=kp,
+                                     style_map=style_map, seam_cols=seam_cols)
         decoded = self.decoder(sampled, rescale=True)
         if mask is not None and composite:
             decoded = (1 - mask) * decoded + mask * content_spec

@@ -456,6 +456,7 @@ def test_graphed_loop_and_set_style_map(ctx, cuda):
 @pytest.mark.parametrize("solver", ["msolver", "ddim"])
 def test_one_prepare_serves_runs_with_other_maps(ctx, cuda, solver):
     """ldm_sample_prepare once, then ldm_sample_run under two different maps: each is the whole ldm_sample, bitwise."""
+    from ldm_amd.engine import LoopOptions
     d = map_inputs(ctx, 2, 16, 64, 2, 183)
     d2 = map_inputs(ctx, 2, 16, 64, 2, 184)
     eng = ctx["M"].engine_for(ctx["ldm"].unet)
@@ -466,12 +467,13 @@ def test_one_prepare_serves_runs_with_other_maps(ctx, cuda, solver):
         x1, x0l1, epl1, coef, t_table = run_loop(ctx, cuda, eng, dict(d, rb5=m["rb5"], rb6=m["rb6"]), TIMES, solver=solver)
         x = z.clone()
         x0l, epl = torch.full_like(x0l1, float("nan")), torch.full_like(epl1, float("nan"))
-        args = (solver, x, s5, s6, t_table, coef, 0.0, x0l, epl, 0, slot)
-        kw = dict(ref_bias5=m["rb5"].to(cuda), ref_bias6=m["rb6"].to(cuda))
+        opts = LoopOptions(x, t_table.shape[0], s5, s6, ref_bias5=m["rb5"].to(cuda), ref_bias6=m["rb6"].to(cuda))
+        opts.check(eng, x, t_table.shape[0])
+        args = (solver, x, opts, t_table, coef, 0.0, x0l, epl, 0, slot)
         if first:
-            eng._sample_call(*args, phase="prepare", **kw)
+            eng._sample_call(*args, phase="prepare")
             first = False
-        eng._sample_call(*args, phase="run", **kw)
+        eng._sample_call(*args, phase="run")
         torch.cuda.synchronize()
         assert bool(torch.isfinite(x1).all())
         assert torch.equal(x, x1) and torch.equal(x0l, x0l1) and torch.equal(epl, epl1)
