@@ -819,6 +819,41 @@ int ldm_adam_step_dev(const ldm_tensor_slot* slots, const int32_t* chunk_tensor,
                       int32_t nchunks, int32_t chunk_len, double lr, double beta1, double beta2, double eps,
                       double weight_decay, int32_t decoupled, float* step, const int32_t* found_inf, float* scalars,
                       void* stream);
+/* ---- gradient-norm clipping and EMA weights inside the optimizer's launches ----
+ * ldm_unscale_check_norm: ldm_unscale_check (same unscale, same flag, inv_scale NULL = 1) that also writes
+ *   partials[i] = the sum over chunk i of (double)g * (double)g of its unscaled gradients (device double
+ *   [nchunks], 8-byte aligned; fixed-order block reduction, one plain store per chunk, no atomics: two runs give
+ *   bitwise equal partials).
+ * ldm_grad_norm_finalize: one block; sum = the partials in ascending chunk order in fp64 (associated by runs of
+ *   ceil(nchunks / 256) consecutive chunks; nchunks <= 256: strictly one after the other);
+ *   out[0] = (float)sqrt(sum); out[1] = (float)min(1, max_norm / (sqrt(sum) + 1e-6)), formed in double:
+ *   torch.nn.utils.clip_grad_norm_'s coefficient (NaN for a NaN norm, 0 for +inf).  max_norm <= 0: norm only,
+ *   out[1] = 1.  Several param groups: one call over the concatenation of their partials (one global norm). */
+int ldm_unscale_check_norm(const ldm_tensor_slot* slots, const int32_t* chunk_tensor, const int64_t* chunk_start,
+                           int32_t nchunks, int32_t chunk_len, const float* inv_scale, int32_t* found_inf,
+                           double* partials, void* stream);
+int ldm_grad_norm_finalize(const double* partials, int64_t nchunks, double max_norm, float* out, void* stream);
+/* ldm_adam_step / ldm_adam_step_dev with the options of one record (NULL record, or all fields NULL: exactly
+ * the plain entry's launch).  The multiplier is applied to the loaded gradient (.grad in memory is not
+ * rewritten); the EMA is updated from the parameter value the step just formed, and is skipped with the step
+ * on found_inf. */
+typedef struct ldm_adam_ext {
+    const float*  grad_mul;  /* device scalar or NULL: g <- g * grad_mul[0], one fp32 multiply, before the weight-decay line */
+    float* const* ema;       /* device array, one pointer per slot (same order as slots), or NULL */
+    double        ema_decay; /* e <- e + (float)(1 - decay) * (p_new - e) (one fused multiply-add), 0 <= decay < 1 */
+} ldm_adam_ext;
+int ldm_adam_step_ext(const ldm_tensor_slot* slots, const int32_t* chunk_tensor, const int64_t* chunk_start,
+                      int32_t nchunks, int32_t chunk_len, double lr, double beta1, double beta2, double eps,
+                      double weight_decay, int32_t decoupled, int32_t step, const int32_t* found_inf,
+                      const ldm_adam_ext* ext, void* stream);
+int ldm_adam_step_dev_ext(const ldm_tensor_slot* slots, const int32_t* chunk_tensor, const int64_t* chunk_start,
+                          int32_t nchunks, int32_t chunk_len, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, int32_t decoupled, float* step, const int32_t* found_inf,
+                          float* scalars, const ldm_adam_ext* ext, void* stream);
+/* The EMA update alone (for callers that step with another optimizer): slot.param = the EMA tensor,
+ * slot.grad = the tensor it follows; e <- e + (float)(1 - decay) * (src - e); skipped when found_inf[0] != 0. */
+int ldm_ema_update(const ldm_tensor_slot* slots, const int32_t* chunk_tensor, const int64_t* chunk_start,
+                   int32_t nchunks, int32_t chunk_len, double decay, const int32_t* found_inf, void* stream);
 /* scaler.update(): scale *= backoff on inf (tracker = 0), *= growth after growth_interval clean steps. */
 int ldm_update_scale(float* scale, int32_t* growth_tracker, const int32_t* found_inf, float growth_factor,
                      float backoff_factor, int32_t growth_interval, void* stream);

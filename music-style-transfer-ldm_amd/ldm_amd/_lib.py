@@ -86,6 +86,11 @@ class SampleArgs(ctypes.Structure):
                 ("log_step_stride", c_int64), ("workspace", c_fp), ("stream", c_vp)]
 
 
+class AdamExt(ctypes.Structure):
+    """ldm_adam_ext: the options of ldm_adam_step_ext / ldm_adam_step_dev_ext (NULL = off)."""
+    _fields_ = [("grad_mul", c_fp), ("ema", c_vp), ("ema_decay", ctypes.c_double)]
+
+
 ACT = {"none": 0, "relu": 1, "tanh": 2, "tanh_half": 3, "gelu": 4}
 DT_ROUND_OUT = 0x100   # ldm_epilogue.dtype flag (ldm_capi.h LDM_DT_ROUND_OUT); act codes: LDM_ACT_ROUND_* = dt << 8
 # 16-bit storage (ldm_capi.h): conv / wgrad dtype flags, and the BatchNorm / activation-backward act-code fields
@@ -270,6 +275,16 @@ SIGNATURES = {
                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int32, c_fp, c_vp, c_fp,
                                     c_vp]),
     "ldm_update_scale": (c_int32, [c_fp, c_vp, c_vp, c_float, c_float, c_int32, c_vp]),
+    # gradient-norm clipping and EMA weights inside the optimizer's launches
+    "ldm_unscale_check_norm": (c_int32, [c_vp, c_vp, c_vp, c_int32, c_int32, c_fp, c_vp, c_vp, c_vp]),
+    "ldm_grad_norm_finalize": (c_int32, [c_vp, c_int64, ctypes.c_double, c_fp, c_vp]),
+    "ldm_adam_step_ext": (c_int32, [c_vp, c_vp, c_vp, c_int32, c_int32, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int32, c_int32, c_vp,
+                                    ctypes.POINTER(AdamExt), c_vp]),
+    "ldm_adam_step_dev_ext": (c_int32, [c_vp, c_vp, c_vp, c_int32, c_int32, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int32, c_fp, c_vp, c_fp,
+                                        ctypes.POINTER(AdamExt), c_vp]),
+    "ldm_ema_update": (c_int32, [c_vp, c_vp, c_vp, c_int32, c_int32, ctypes.c_double, c_vp, c_vp]),
 }
 
 # ldm_tensor_slot: 4 device pointers + int64 numel, packed into an int64 tensor on the device

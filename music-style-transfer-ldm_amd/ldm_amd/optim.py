@@ -6,9 +6,15 @@ step() is ONE multi-tensor launch per param group (ldm_adam_step).  ``GradScaler
 torch.amp.GradScaler's API and semantics (scale / unscale_ / step / update, backoff and growth) with
 the unscale + inf check and the scale update as device kernels (ldm_unscale_check, ldm_update_scale).
 
+Not in the reference, off by default: gradient-norm clipping (clip_grad_norm_, grad_norm_coef,
+GradScaler.unscale_(optimizer, max_norm=): the norm is formed by the unscale launch, the coefficient multiplies
+the gradients inside the Adam launch) and an EMA of the parameters updated inside the Adam launch (Adam.attach_ema).
+
 Reference call sites: torch.optim.Adam + torch.amp.GradScaler in LDMTrainer (train.py:156-157,
 :189-201); torch.optim.AdamW in train_autoencoder (train.py:44).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -148,6 +154,123 @@ def scale_tensors_(tensors, factor):
     return bad
 
 
+class _NormBuffers:
+    """Device buffers of one gradient-norm pass: per-chunk fp64 partial sums, the [norm, coef] fp32 pair the
+    finalize writes, and an inf/nan flag.  Like a slot table they are read by captured launches at every replay,
+    so they are allocated outside any capture only (a buffer allocated while capturing comes from the graph's
+    private pool and may be a block the same capture's scratch rewrites: see _SlotTable) and reused by every
+    step.  Sized by the chunk count: a gradient set of other sizes gets another one, outside capture."""
+
+    def __init__(self, dev, nchunks):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ldm_amd.optim: the gradient-norm buffers are allocated outside a graph capture only "
+                               "(run the clipped step eagerly once before capturing it)")
+        self.nchunks = int(nchunks)
+        self.partials = torch.zeros(max(1, self.nchunks), dtype=torch.float64, device=dev)
+        self.pair = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.found_inf = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    @classmethod
+    def get(cls, cache, dev, nchunks):
+        buf = cache.get((dev, nchunks))
+        if buf is None:
+            if len(cache) > 8:
+                cache.clear()
+            buf = cache[(dev, nchunks)] = cls(dev, nchunks)
+        return buf
+
+
+def _norm_pass(groups, max_norm, inv_scale, cache, found_inf=None):
+    """ldm_unscale_check_norm over every list of parameters in `groups` (one table each), then one finalize
+    over the concatenated partials: one global norm.  Returns (buffers, tables)."""
+    groups = [ps for ps in groups if ps]
+    tabs = []
+    for ps in groups:
+        _check_params(ps)
+        tabs.append(_SlotTable(ps, [p.grad for p in ps], [None] * len(ps), [None] * len(ps)))
+    dev = groups[0][0].device
+    buf = _NormBuffers.get(cache, dev, sum(t.nchunks for t in tabs))
+    flag = buf.found_inf if found_inf is None else found_inf
+    off = 0
+    for tab in tabs:
+        L.call("ldm_unscale_check_norm", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
+               tab.nchunks, CHUNK, None if inv_scale is None else inv_scale.data_ptr(), flag.data_ptr(),
+               buf.partials.data_ptr() + 8 * off, stream_handle())
+        off += tab.nchunks
+    L.call("ldm_grad_norm_finalize", buf.partials.data_ptr(), buf.nchunks, float(max_norm), buf.pair.data_ptr(),
+           stream_handle())
+    return buf, tabs
+
+
+_norm_cache = {}
+
+
+def _grad_params(parameters):
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    return [p for p in parameters if p.grad is not None and p.numel()]
+
+
+def grad_norm_coef(parameters, max_norm):
+    """The global 2-norm of the parameters' gradients and torch.nn.utils.clip_grad_norm_'s coefficient
+    min(1, max_norm / (norm + 1e-6)) as a device fp32 pair [norm, coef]; the gradients are left as they are.
+    One norm launch plus a one-block finalize, fixed-order fp64 sums, no host synchronisation.  max_norm <= 0:
+    norm only (coef = 1).  The pair is a buffer that the next call with gradients of the same sizes rewrites:
+    pass pair[1:2] to Adam.step(grad_mul=...) for a clipped step that does not rewrite the gradients."""
+    ps = _grad_params(parameters)
+    if not ps:
+        raise ValueError("ldm_amd.optim.grad_norm_coef: no parameter has a gradient")
+    buf, tabs = _norm_pass([ps], max_norm, None, _norm_cache)
+    buf.tabs = tabs   # keep alive until the launches ran
+    return buf.pair
+
+
+def clip_grad_norm_(parameters, max_norm):
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2) on the device: the norm pass, the
+    finalize, then grad *= coef in one ldm_unscale_check launch with the device coefficient as its factor.
+    Returns the norm (before clipping) as a 0-d device tensor.  No host synchronisation; deterministic."""
+    ps = _grad_params(parameters)
+    if not ps:
+        raise ValueError("ldm_amd.optim.clip_grad_norm_: no parameter has a gradient")
+    buf, tabs = _norm_pass([ps], max_norm, None, _norm_cache)
+    tab = tabs[0]
+    L.call("ldm_unscale_check", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
+           tab.nchunks, CHUNK, buf.pair.data_ptr() + 4, buf.found_inf.data_ptr(), stream_handle())
+    buf.tabs = tabs
+    return buf.pair[0].clone()
+
+
+def ema_update_(ema_tensors, sources, decay, found_inf=None):
+    """e <- e + (1 - decay) (src - e) for every pair, one multi-tensor launch (ldm_ema_update): the EMA update of
+    Adam.attach_ema on its own, for callers that step with another optimizer."""
+    _check_decay(decay)
+    pairs = [(e, s) for e, s in zip(ema_tensors, sources) if e.numel()]
+    if not pairs:
+        return
+    es, ss = [e for e, _ in pairs], [s for _, s in pairs]
+    require_device(*es, *ss, what="ema_update_")
+    tab = _SlotTable(es, ss, [None] * len(es), [None] * len(es))
+    L.call("ldm_ema_update", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
+           tab.nchunks, CHUNK, float(decay), None if found_inf is None else found_inf.data_ptr(), stream_handle())
+    return tab
+
+
+def _check_decay(decay):
+    if not isinstance(decay, (int, float)) or isinstance(decay, bool) or not 0.0 <= decay < 1.0:
+        raise ValueError(f"Invalid EMA decay: {decay} (0 <= decay < 1)")
+
+
+def ema_state_dict(module, optimizer):
+    """module.state_dict() with every parameter that `optimizer` keeps an EMA of replaced by that EMA; buffers
+    and the other parameters are copied as they are."""
+    sd = {k: v.detach().clone() for k, v in module.state_dict().items()}
+    for name, p in module.named_parameters():
+        e = optimizer.state.get(p, {}).get("ema")
+        if e is not None and name in sd:
+            sd[name] = e.detach().clone()
+    return sd
+
+
 def _check_params(params):
     for p in params:
         require_device(p, what="ldm_amd.optim")
@@ -178,10 +301,82 @@ class Adam(torch.optim.Optimizer):
         # capturable (torch.optim.Adam(capturable=True)): the step count is a device tensor advanced by the
         # kernel itself, so step() never reads it on the host and can be captured into a hipGraph
         self.capturable = bool(capturable)
+        self.ema_decay = None     # attach_ema
+        self._ema_ptrs = {}
 
     @torch.no_grad()
-    def step(self, closure=None, found_inf=None):
-        """One Adam update.  found_inf (device int32 [1], optional): skip on the device if set."""
+    def attach_ema(self, decay):
+        """Keep an exponential moving average of every parameter, e <- e + (1 - decay) (p - e), updated inside the
+        step's own launch from the parameter value the step just formed (skipped with the step on inf/nan).  The
+        EMA tensors start at the parameters and live in state[p]["ema"], so state_dict / load_state_dict carry
+        them."""
+        _check_decay(decay)
+        if self.ema_decay is not None:
+            raise RuntimeError("ldm_amd.optim: attach_ema was already called on this optimizer")
+        self.ema_decay = float(decay)
+        self._init_ema()
+
+    def _init_ema(self):
+        """An EMA tensor for every parameter that has none (initialised to the parameter) and the device pointer
+        arrays of the groups' full parameter lists (built here, outside any capture)."""
+        self._ema_ptrs.clear()
+        for group in self.param_groups:
+            for p in group["params"]:
+                st = self.state[p]
+                if "ema" not in st:
+                    st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
+            ps = list(group["params"])
+            if ps and ps[0].device.type == "cuda":
+                self._ema_pointer_array(ps)
+
+    def ema_tensors(self):
+        """[(parameter, its EMA tensor)] over all groups, in group order."""
+        return [(p, self.state[p]["ema"]) for g in self.param_groups for p in g["params"] if "ema" in self.state[p]]
+
+    def _ema_pointer_array(self, ps):
+        """Device int64 array of the EMA tensors' addresses, one per slot of the table over `ps`.  Read by
+        captured launches at every replay, so built and filled outside any capture only (see _SlotTable)."""
+        es = [self.state[p]["ema"] for p in ps]
+        key = tuple(e.data_ptr() for e in es)
+        hit = self._ema_ptrs.get(key)
+        if hit is not None:
+            return hit[0]
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ldm_amd.optim: the EMA pointer array is built outside a graph capture only "
+                               "(attach_ema builds it for a group's full parameter list; run the step eagerly "
+                               "once before capturing a step over another set)")
+        for p, e in zip(ps, es):
+            require_device(e, what="ldm_amd.optim EMA")
+            if not e.is_contiguous() or e.numel() != p.numel() or e.dtype != torch.float32:
+                raise RuntimeError("ldm_amd.optim: an EMA tensor must be contiguous fp32 of its parameter's size")
+        host = torch.tensor(key, dtype=torch.int64).pin_memory()
+        arr = torch.empty(len(key), dtype=torch.int64, device=ps[0].device)
+        arr.copy_(host, non_blocking=True)
+        if len(self._ema_ptrs) > 16:
+            self._ema_ptrs.clear()
+        self._ema_ptrs[key] = (arr, host)
+        return arr
+
+    def _ext(self, ps, grad_mul):
+        """The ldm_adam_ext record of a launch over `ps`, or None when neither option is set."""
+        if grad_mul is None and self.ema_decay is None:
+            return None
+        ext = L.AdamExt(None, None, 0.0)
+        if grad_mul is not None:
+            require_device(grad_mul, what="ldm_amd.optim grad_mul")
+            if grad_mul.dtype != torch.float32 or grad_mul.numel() != 1:
+                raise RuntimeError("ldm_amd.optim: grad_mul is a device fp32 scalar")
+            ext.grad_mul = grad_mul.data_ptr()
+        if self.ema_decay is not None:
+            ext.ema = self._ema_pointer_array(ps).data_ptr()
+            ext.ema_decay = self.ema_decay
+        return ext
+
+    @torch.no_grad()
+    def step(self, closure=None, found_inf=None, grad_mul=None):
+        """One Adam update.  found_inf (device int32 [1], optional): skip on the device if set.  grad_mul (device
+        fp32 scalar, optional): every gradient is multiplied by it as it is loaded (a clip coefficient);
+        .grad itself is not rewritten."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -193,7 +388,7 @@ class Adam(torch.optim.Optimizer):
             _check_params(params)
             beta1, beta2 = group["betas"]
             if self.capturable:
-                self._step_capturable(gi, group, params, found_inf, beta1, beta2)
+                self._step_capturable(gi, group, params, found_inf, beta1, beta2, grad_mul)
                 continue
             if "_ldm_step" in group:
                 # leaving the capturable form: every param gets its own host step count again (the shared
@@ -203,7 +398,7 @@ class Adam(torch.optim.Optimizer):
             by_step = {}
             for p in params:
                 st = self.state[p]
-                if len(st) == 0:
+                if "step" not in st:     # (an attached EMA is in the state before the first step)
                     st["step"] = torch.tensor(0.0)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
@@ -213,10 +408,15 @@ class Adam(torch.optim.Optimizer):
                 grads = [p.grad for p in ps]
                 tab = _SlotTable(ps, grads, [self.state[p]["exp_avg"] for p in ps],
                                  [self.state[p]["exp_avg_sq"] for p in ps])
-                L.call("ldm_adam_step", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-                       tab.nchunks, CHUNK, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                       float(group["weight_decay"]), self._decoupled, step,
-                       None if found_inf is None else found_inf.data_ptr(), stream_handle())
+                ext = self._ext(ps, grad_mul)
+                args = (tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
+                        tab.nchunks, CHUNK, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
+                        float(group["weight_decay"]), self._decoupled, step,
+                        None if found_inf is None else found_inf.data_ptr())
+                if ext is None:
+                    L.call("ldm_adam_step", *args, stream_handle())
+                else:
+                    L.call("ldm_adam_step_ext", *args, ctypes.byref(ext), stream_handle())
                 # the tables are read by the kernel asynchronously: keep them alive until it ran
                 self._tables[(gi, step)] = tab
                 # the kernel wrote the parameters through raw pointers: move their autograd versions the
@@ -265,16 +465,19 @@ class Adam(torch.optim.Optimizer):
                 if st and "step" in st and torch.is_tensor(st["step"]):
                     st["step"] = torch.tensor(float(st["step"]))
         self._tables.clear()
+        if self.ema_decay is not None:
+            # the loaded EMA tensors are new ones; a state dict without them re-initialises the EMA from the parameters
+            self._init_ema()
         # a captured train step holds the old state tensors: LDMTrainer re-captures when this moves
         self.state_epoch = getattr(self, "state_epoch", 0) + 1
 
-    def _step_capturable(self, gi, group, params, found_inf, beta1, beta2):
+    def _step_capturable(self, gi, group, params, found_inf, beta1, beta2, grad_mul=None):
         """One launch pair for the group: ldm_adam_step_dev advances the group's device step count (shared
         by its params' state["step"]) unless found_inf is set and forms the scalars from it on the device."""
         dev = params[0].device
         gstep = group.get("_ldm_step")
         if gstep is None:
-            prev = [self.state[p]["step"] for p in params if len(self.state[p]) > 0]
+            prev = [self.state[p]["step"] for p in params if "step" in self.state[p]]
             init = float(prev[0]) if prev else 0.0
             if any(float(s) != init for s in prev):
                 raise RuntimeError("ldm_amd.optim.Adam(capturable=True): params of a group at different steps")
@@ -289,10 +492,15 @@ class Adam(torch.optim.Optimizer):
             st["step"] = gstep
         tab = _SlotTable(params, [p.grad for p in params], [self.state[p]["exp_avg"] for p in params],
                          [self.state[p]["exp_avg_sq"] for p in params])
-        L.call("ldm_adam_step_dev", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-               tab.nchunks, CHUNK, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-               float(group["weight_decay"]), self._decoupled, gstep.data_ptr(),
-               None if found_inf is None else found_inf.data_ptr(), group["_ldm_scalars"].data_ptr(), stream_handle())
+        ext = self._ext(params, grad_mul)
+        args = (tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
+                tab.nchunks, CHUNK, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
+                float(group["weight_decay"]), self._decoupled, gstep.data_ptr(),
+                None if found_inf is None else found_inf.data_ptr(), group["_ldm_scalars"].data_ptr())
+        if ext is None:
+            L.call("ldm_adam_step_dev", *args, stream_handle())
+        else:
+            L.call("ldm_adam_step_dev_ext", *args, ctypes.byref(ext), stream_handle())
         self._tables[(gi, "dev")] = tab
         for p in params:
             torch.autograd.graph.increment_version(p)
@@ -327,6 +535,9 @@ class GradScaler:
         self._found_inf = None
         self._unscaled = set()
         self._divisor = 1.0
+        self.last_grad_norm = None   # device 0-d fp32: the last unscale_(max_norm=...)'s gradient norm
+        self._clip_coef = None       # device fp32 [1]: its clip coefficient, the next step()'s gradient multiplier
+        self._norm_cache = {}
 
     def is_enabled(self):
         return self._enabled
@@ -350,13 +561,29 @@ class GradScaler:
         self._lazy_init(outputs.device)
         return outputs * self._scale.to(outputs.device)
 
-    def unscale_(self, optimizer):
+    def unscale_(self, optimizer, max_norm=None):
+        """scaler.unscale_.  max_norm (optional): the same launches also form the global 2-norm of the unscaled
+        gradients (ldm_unscale_check_norm) and a one-block finalize leaves [norm, coef] on the device:
+        last_grad_norm (0-d) and _clip_coef, which step() hands to the optimizer as its gradient multiplier
+        (torch.nn.utils.clip_grad_norm_'s coefficient; max_norm <= 0: norm only)."""
+        if max_norm is not None and not self._enabled:
+            raise RuntimeError("ldm_amd.optim.GradScaler: a disabled scaler does not clip; use clip_grad_norm_")
         if not self._enabled or id(optimizer) in self._unscaled:
             return
         self._lazy_init(next(p.device for g in optimizer.param_groups for p in g["params"]))
         # GradScaler: scale.double().reciprocal().float()  (x 1/divisor for data-parallel averaging)
         inv = torch.reciprocal(self._scale.double() * self._divisor).float()
         self._found_inf.zero_()
+        if max_norm is not None:
+            groups = [[p for p in g["params"] if p.grad is not None] for g in optimizer.param_groups]
+            if any(groups):
+                buf, tabs = _norm_pass(groups, max_norm, inv, self._norm_cache, self._found_inf)
+                optimizer.param_groups[0].setdefault("_ldm_tabs", []).extend(tabs)   # keep alive until the launches ran
+                self.last_grad_norm = buf.pair[0]
+                self._clip_coef = buf.pair[1:2] if max_norm > 0 else None
+            self._unscaled.add(id(optimizer))
+            return
+        self.last_grad_norm = self._clip_coef = None
         for group in optimizer.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -374,6 +601,8 @@ class GradScaler:
         self.unscale_(optimizer)
         for group in optimizer.param_groups:
             group.pop("_ldm_tabs", None)
+        if self._clip_coef is not None:
+            kwargs["grad_mul"] = self._clip_coef
         if getattr(optimizer, "capturable", False):
             # device-side skip: the kernel pair reads found_inf and leaves the step count alone on inf/nan
             return optimizer.step(*args, found_inf=self._found_inf, **kwargs)
@@ -393,6 +622,7 @@ class GradScaler:
                    float(self._growth_factor), float(self._backoff_factor), int(self._growth_interval),
                    stream_handle())
         self._unscaled.clear()
+        self._clip_coef = None   # (last_grad_norm stays readable until the next unscale_)
 
     def state_dict(self):
         if not self._enabled:

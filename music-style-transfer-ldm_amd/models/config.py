@@ -9,6 +9,8 @@ Notes on keys this implementation reads:
                                    see loss.set_perceptual_backend), 'vggish' -> VGGishFeatureLoss
   training_iteration_noise         multiplier applied to epoch-average losses (reporting only,
                                    reference train.py:240-243)
+  max_grad_norm, ema_decay         additions of this implementation, None = off (train.py: LDMTrainer,
+                                   train_autoencoder)
 """
 
 _optimizer = dict(
@@ -16,6 +18,10 @@ _optimizer = dict(
     learning_rate_factor=0.5,
     learning_rate_patience=5,
     learning_rate_min=1e-6,
+    # not in the reference (None = off, the reference's step): clip the global gradient 2-norm to this value /
+    # keep an exponential moving average of the weights with this decay (ldm_amd.optim)
+    max_grad_norm=None,
+    ema_decay=None,
 )
 
 _schedule = dict(

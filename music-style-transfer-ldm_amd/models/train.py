@@ -20,6 +20,7 @@ Differences from the reference, all deliberate:
     reference-style `dataset` module from sys.path.
 """
 import argparse
+import contextlib
 import os
 from collections.abc import Mapping
 
@@ -62,10 +63,12 @@ def _prepare_loaders(cfg):
 
 
 # ------------------------------------------------------------------------------------------------
-def autoencoder_step(encoder, decoder, optimizer, spectrogram, feature_extractor, reducer=None):
+def autoencoder_step(encoder, decoder, optimizer, spectrogram, feature_extractor, reducer=None, max_grad_norm=None):
     """One inner iteration of train_autoencoder (reference train.py:69-82): encode -> decode ->
     compression_loss -> zero_grad -> backward (-> data-parallel gradient all-reduce) -> AdamW step.
-    Returns the loss tensor (the caller's .item() is the reference's host sync)."""
+    Returns the loss tensor (the caller's .item() is the reference's host sync).  max_grad_norm (not in the
+    reference): the gradients' global norm is formed on the device and the clip coefficient multiplies them
+    inside the AdamW launch; an EMA attached to the optimizer (attach_ema) is updated in the same launch."""
     latent = encoder(spectrogram)
     reconstructed = decoder(latent)
     loss = compression_loss(spectrogram, reconstructed, latent, feature_extractor)
@@ -73,7 +76,11 @@ def autoencoder_step(encoder, decoder, optimizer, spectrogram, feature_extractor
     loss.backward()
     if reducer is not None:
         reducer.finish()
-    optimizer.step()
+    if max_grad_norm is not None:
+        pair = hoptim.grad_norm_coef([p for g in optimizer.param_groups for p in g["params"]], max_grad_norm)
+        optimizer.step(grad_mul=pair[1:2])
+    else:
+        optimizer.step()
     return loss
 
 
@@ -85,6 +92,9 @@ def train_autoencoder(config, train_loader=None, test_loader=None, device=None):
     decoder = SpectrogramDecoder(config["latent_dim_encoder"]).to(device)
     feature_extractor = VGGishFeatureLoss().to(device)
     optimizer = hoptim.AdamW(list(encoder.parameters()) + list(decoder.parameters()), lr=config["learning_rate"])
+    max_grad_norm, ema_decay = config.get("max_grad_norm"), config.get("ema_decay")
+    if ema_decay is not None:
+        optimizer.attach_ema(ema_decay)
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(
         optimizer, mode="min", factor=config["learning_rate_factor"], patience=config["learning_rate_patience"],
         min_lr=config["learning_rate_min"])
@@ -106,7 +116,8 @@ def train_autoencoder(config, train_loader=None, test_loader=None, device=None):
         decoder.train()
         for spectrogram in train_loader:
             spectrogram = spectrogram[0].to(device)
-            loss = autoencoder_step(encoder, decoder, optimizer, spectrogram, feature_extractor, reducer)
+            loss = autoencoder_step(encoder, decoder, optimizer, spectrogram, feature_extractor, reducer,
+                                    max_grad_norm=max_grad_norm)
             running += loss.item()
         avg_train = running / max(1, len(train_loader))
         train_losses.append(avg_train)
@@ -136,6 +147,9 @@ def train_autoencoder(config, train_loader=None, test_loader=None, device=None):
     if hdist.rank() == 0:
         torch.save(encoder.state_dict(), "models/pretrained/encoder.pth")
         torch.save(decoder.state_dict(), "models/pretrained/decoder.pth")
+        if ema_decay is not None:
+            torch.save(hoptim.ema_state_dict(encoder, optimizer), "models/pretrained/encoder_ema.pth")
+            torch.save(hoptim.ema_state_dict(decoder, optimizer), "models/pretrained/decoder_ema.pth")
     return train_losses, val_losses
 
 
@@ -174,7 +188,8 @@ class StepLosses(Mapping):
 class LDMTrainer:
     """Reference train.py:140-293."""
 
-    def __init__(self, model, train_loader, device, lr=1e-4, style_loss_weight=0.1):
+    def __init__(self, model, train_loader, device, lr=1e-4, style_loss_weight=0.1, max_grad_norm=None,
+                 ema_decay=None):
         self.model = model.to(device)
         self.train_loader = train_loader
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
@@ -183,6 +198,14 @@ class LDMTrainer:
         self._trainable = trainable_params
         self.optimizer = hoptim.Adam(trainable_params, lr=lr)
         self.scaler = hoptim.GradScaler("cuda")
+        # Not in the reference, both off by default (None: the step launches exactly what it launched without them).
+        # max_grad_norm: the global 2-norm of the unscaled (and, data-parallel, all-reduced) gradients is formed
+        # inside the unscale launch and torch's clip coefficient multiplies the gradients inside the Adam launch;
+        # ema_decay: the optimizer keeps an EMA of the trainable weights, updated inside the Adam launch.
+        self.max_grad_norm = max_grad_norm
+        self.ema_decay = ema_decay
+        if ema_decay is not None:
+            self.optimizer.attach_ema(ema_decay)
         # dtype of the train step's autocast region (train.py:174 uses the device default: fp16 on a GPU;
         # bfloat16 = BASELINE config 3); the HIP convs then round their operands to it (ldm_capi.h LDM_DT_*)
         self.autocast_dtype = None
@@ -264,6 +287,9 @@ class LDMTrainer:
             self.scaler.scale(total_loss).backward()
         if self.reducer is not None:
             self.reducer.finish()
+        if self.max_grad_norm is not None:
+            # after the all-reduce: every rank forms the same norm from the same gradients, no extra collective
+            self.scaler.unscale_(self.optimizer, max_norm=self.max_grad_norm)
         self.scaler.step(self.optimizer)
         self.scaler.update()
         if rec is not None:
@@ -300,7 +326,7 @@ class LDMTrainer:
         hyper = tuple((g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]) for g in self.optimizer.param_groups)
         sig = tuple(None if a is None else (tuple(a.shape), a.dtype) for a in args) + (
             hyper, self.style_loss_weight, self.autocast_enabled, self.autocast_dtype,
-            getattr(self.optimizer, "state_epoch", 0))
+            getattr(self.optimizer, "state_epoch", 0), self.max_grad_norm, self.ema_decay)
         if self._graph is None or self._graph_sig != sig:
             if self._graph_calls < self.graph_warmup:
                 self._graph_calls += 1
@@ -340,6 +366,39 @@ class LDMTrainer:
         if self._packset is not None:
             self._packset.rekey()      # the replay ended by re-packing them from the updated weights
         return self._losses(self._graph_out)
+
+    @property
+    def last_grad_norm(self):
+        """The last step's gradient norm (before clipping) as a 0-d device tensor; None when clipping is off."""
+        return None if self.max_grad_norm is None else self.scaler.last_grad_norm
+
+    def ema_state_dict(self):
+        """The model's state dict with every trainable parameter replaced by its EMA (buffers and frozen
+        parameters copied as they are)."""
+        if self.ema_decay is None:
+            raise RuntimeError("LDMTrainer.ema_state_dict: the trainer keeps no EMA (ema_decay=None)")
+        return hoptim.ema_state_dict(self.model, self.optimizer)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the trainable parameters hold their EMA values (e.g. for LDM.content_style_transfer
+        on the averaged weights); on exit the raw values are back, bitwise.  Device copies; the parameters'
+        autograd versions move both ways, so packed-weight caches and the UNet engine re-pack."""
+        if self.ema_decay is None:
+            raise RuntimeError("LDMTrainer.ema_weights: the trainer keeps no EMA (ema_decay=None)")
+        pairs = self.optimizer.ema_tensors()
+        with torch.no_grad():
+            raw = [p.detach().clone() for p, _ in pairs]
+            for p, e in pairs:
+                p.detach().copy_(e)
+                torch.autograd.graph.increment_version(p)
+        try:
+            yield self.model
+        finally:
+            with torch.no_grad():
+                for (p, _), r in zip(pairs, raw):
+                    p.detach().copy_(r)
+                    torch.autograd.graph.increment_version(p)
 
     def graph_inputs(self):
         """The captured step's static input buffers (content, style, t, noise; None until the graph exists or
@@ -381,6 +440,8 @@ class LDMTrainer:
             if epoch % 100 == 0 and hdist.rank() == 0:
                 os.makedirs("models/pretrained", exist_ok=True)
                 torch.save(self.model.state_dict(), f"models/pretrained/ldm_{epoch}.pth")
+                if self.ema_decay is not None:
+                    torch.save(self.ema_state_dict(), f"models/pretrained/ldm_ema_{epoch}.pth")
         return train_losses, compression_losses, denoise_losses, style_losses
 
 
@@ -396,7 +457,8 @@ def train_ldm(config, train_loader=None, device=None):
         train_loader = torch.utils.data.DataLoader(train_dataset, batch_size=config["batch_size"], shuffle=True,
                                                    num_workers=0)
     trainer = LDMTrainer(model, train_loader, device, lr=config["learning_rate"],
-                         style_loss_weight=config["style_loss_weight"])
+                         style_loss_weight=config["style_loss_weight"], max_grad_norm=config.get("max_grad_norm"),
+                         ema_decay=config.get("ema_decay"))
     return trainer.train(config["num_epochs"])
 
 
