@@ -66,6 +66,29 @@ struct UArgs {
     // {a, b, scale[B]}, so e_b is still read from `skip` and the strengths from `bcast`, two floats further on
 };
 
+// What a launch's head reads before its first operand load, passed as plain leading kernel parameters in front of
+// UArgs (13 dwords): gfx950 delivers leading scalar parameters in SGPRs at wave launch (kernarg preload, enabled per
+// translation unit in the Makefile), so the descriptors, the tile decode and the column arithmetic start without
+// waiting for the kernarg segment's cold scalar load.  A by-value struct is not preloaded, hence plain parameters;
+// UArgs keeps what the epilogue and the general decode read.  make_head fills it from the finished UArgs.
+struct UHead {
+    const float* w;       // = UArgs::w
+    const float* x;       // = UArgs::x
+    int32_t xbytes;       // bytes of x (the activation buffer descriptor's range)
+    uint32_t dec;         // block order in bits 0-1; order 2: log2 xpn in bits 2-3, log2(nMt / xpm) in bits 4-7,
+                          // nNt / xpn in bits 8-31 (set_grid takes order 2 only where these are exact)
+    int32_t tiles;        // nMt * nNt
+    int32_t Nq, Hin, Win;
+    uint32_t mul_hw, mul_w;   // FastDiv::mul of fd_hw / fd_w
+    uint32_t shr;         // fd_hw: shr in bits 0-4, `one` in bit 5; fd_w: the same in bits 8-12, 13
+    __device__ __forceinline__ int div_hw(int n) const {
+        return (int)((__umulhi((uint32_t)n, mul_hw) >> (shr & 31u)) + ((uint32_t)n & (0u - ((shr >> 5) & 1u))));
+    }
+    __device__ __forceinline__ int div_w(int n) const {
+        return (int)((__umulhi((uint32_t)n, mul_w) >> ((shr >> 8) & 31u)) + ((uint32_t)n & (0u - ((shr >> 13) & 1u))));
+    }
+};
+
 // (ky, kx) of tap t and the conv input offset / the transposed conv's output parity
 __host__ __device__ constexpr int tky(int t) { return t / 3; }
 __host__ __device__ constexpr int tkx(int t) { return t % 3; }
@@ -138,7 +161,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 template <int MODE, int CIN, int COUT, int TM, int TN, int WN, int WK, int NCH, int S, int EPI, int DT, int KS, int TC = 0>
-__device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
+__device__ __forceinline__ void uconv_body(const UHead& h, const UArgs& a, int bid_in) {
     constexpr int NPH = tc_nph(MODE, TC);         // accumulator sets: the output parities this block finishes
     constexpr int NST = NCH / S;
     constexpr int CPC = tc_ntap(TC);              // chunks per channel chunk (the 9 taps, or the taps of class TC)
@@ -164,17 +187,18 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
         int bid = bid_in;
         if constexpr (KS > 1) {
             ks = a.fd_tiles.div(bid);
-            bid -= ks * (a.nMt * a.nNt);
+            bid -= ks * h.tiles;
         }
-        if (a.order == 2) {
+        if ((h.dec & 3u) == 2u) {
             // XCD-aware: tile T goes to XCD T % 8 (round-robin placement); XCD x = (xm, xn) owns the contiguous
             // M-tile slice xm and N-tile slice xn, so it fetches 1/xpm of the weights and 1/xpn of the input
-            // (and the input rows a slice shares with its neighbour once)
+            // (and the input rows a slice shares with its neighbour once).  xpn and the M tiles per slice are
+            // powers of two (set_grid): the decode is shifts and masks of the preloaded record
+            const int spn = (h.dec >> 2) & 3u, sml = (h.dec >> 4) & 15u, nloc = (int)(h.dec >> 8);
             const int x = bid & 7, l = bid >> 3;
-            const int xm = x / a.xpn, xn = x - xm * a.xpn;
-            const int mloc = a.nMt / a.xpm, nloc = a.nNt / a.xpn;
-            const int ln = l / mloc;
-            mt = xm * mloc + (l - ln * mloc);
+            const int xm = x >> spn, xn = x & ((1 << spn) - 1);
+            const int ln = l >> sml;
+            mt = (xm << sml) + (l & ((1 << sml) - 1));
             nt = xn * nloc + ln;
         } else {
             const int q1 = a.fd_mt.div(bid), q2 = a.fd_nt.div(bid);
@@ -190,41 +214,44 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
     int vt[9][TN];
     int cb[TN], cqy[TN], cqx[TN];
     bool cval[TN];
+    // (the column grid from the preloaded input plane: output pixels of a conv, input pixels of a transposed one)
+    const int Hin = h.Hin, Win = h.Win;
+    const int Hq = MODE == 1 ? Hin / 2 : Hin, Wq = MODE == 1 ? Win / 2 : Win;
 #pragma unroll
     for (int ni = 0; ni < TN; ++ni) {
         const int n = nbase + 16 * ni + col;
-        const bool nv = n < a.Nq;
+        const bool nv = n < h.Nq;
         const int nn = nv ? n : 0;
-        const int b = a.fd_hw.div(nn);
-        const int r = nn - b * (a.Hq * a.Wq);
-        const int qy = a.fd_w.div(r);
-        const int qx = r - qy * a.Wq;
+        const int b = h.div_hw(nn);
+        const int r = nn - b * (Hq * Wq);
+        const int qy = h.div_w(r);
+        const int qx = r - qy * Wq;
         cb[ni] = b;
         cqy[ni] = qy;
         cqx[ni] = qx;
         cval[ni] = nv;
         const int iy0 = MODE == 0 ? qy - 1 : (MODE == 1 ? 2 * qy - 1 : qy);
         const int ix0 = MODE == 0 ? qx - 1 : (MODE == 1 ? 2 * qx - 1 : qx);
-        const int base = ((b * a.Hin + iy0) * a.Win + ix0) * (CIN * 4) + lg * 16;
+        const int base = ((b * Hin + iy0) * Win + ix0) * (CIN * 4) + lg * 16;
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int ky = tky(t), kx = tkx(t);
             const int dy = MODE == 2 ? (ky == 0 ? 1 : 0) : ky;
             const int dx = MODE == 2 ? (kx == 0 ? 1 : 0) : kx;
-            const bool ok = nv && (unsigned)(iy0 + dy) < (unsigned)a.Hin && (unsigned)(ix0 + dx) < (unsigned)a.Win;
-            vt[t][ni] = ok ? base + (dy * a.Win + dx) * (CIN * 4) : kOOB;
+            const bool ok = nv && (unsigned)(iy0 + dy) < (unsigned)Hin && (unsigned)(ix0 + dx) < (unsigned)Win;
+            vt[t][ni] = ok ? base + (dy * Win + dx) * (CIN * 4) : kOOB;
         }
     }
 
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-        uni_ptr(a.x), (short)0, uni(a.B * a.Hin * a.Win * CIN * 4), 0x00020000);
+        uni_ptr(h.x), (short)0, uni(h.xbytes), 0x00020000);
     // 16-bit operands read 16-bit packed weights (ldm_step_pack_weight_dt): half the A bytes of the fp32 pack,
     // which matters because a block's operand stream through its CU's L1 is what bounds these launches
     constexpr int AE = DT != 0 ? 2 : 4;                        // bytes per packed weight element
     using AT = std::conditional_t<DT != 0, shortx4, floatx4>;
     constexpr int WBYTES = 9 * CIN * COUT * AE;
     const __amdgpu_buffer_rsrc_t wr =
-        __builtin_amdgcn_make_buffer_rsrc(uni_ptr(a.w), (short)0, WBYTES, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(uni_ptr(h.w), (short)0, WBYTES, 0x00020000);
     const int va = ((m0 + col) * 16 + lg * 4) * AE;            // A: row m0+col, k-local 4*lg .. +3
     const int kw0 = ks * WK + wk;                              // this wave's slice of K
     const int sa0 = uni(kw0 * (NCH / CPC) * 9 * COUT * 16 * AE);   // first chunk (tap 0) of its first channel chunk
@@ -530,10 +557,10 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
         constexpr int WC = MODE == 0 ? 16 * TN + 2 : (MODE == 1 ? 32 * TN + 1 : 16 * TN + 1);
         constexpr int WPOS = WR * WC;          // window positions
         constexpr int NLD = (WPOS * 4 + 63) / 64;   // 16-byte loads per lane per channel chunk
-        const int b0 = a.fd_hw.div(nbase);
-        const int rem = nbase - b0 * (a.Hq * a.Wq);
-        const int y0 = a.fd_w.div(rem);
-        const int x0 = rem - y0 * a.Wq;
+        const int b0 = h.div_hw(nbase);
+        const int rem = nbase - b0 * (Hq * Wq);
+        const int y0 = h.div_w(rem);
+        const int x0 = rem - y0 * Wq;
         const int iy0 = MODE == 0 ? y0 - 1 : (MODE == 1 ? 2 * y0 - 1 : y0);
         const int ix0 = MODE == 0 ? x0 - 1 : (MODE == 1 ? 2 * x0 - 1 : x0);
         floatx4 wl[NCC][NLD];
@@ -544,8 +571,8 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
             const int pos = e >> 2, g4 = e & 3;
             const int r = pos / WC, cx = pos - r * WC;
             const int iy = iy0 + r, ix = ix0 + cx;
-            const bool ok = e < WPOS * 4 && (unsigned)iy < (unsigned)a.Hin && (unsigned)ix < (unsigned)a.Win && nbase < a.Nq;
-            const int off = ok ? ((b0 * a.Hin + iy) * a.Win + ix) * (CIN * 4) + g4 * 16 : kOOB;
+            const bool ok = e < WPOS * 4 && (unsigned)iy < (unsigned)Hin && (unsigned)ix < (unsigned)Win && nbase < h.Nq;
+            const int off = ok ? ((b0 * Hin + iy) * Win + ix) * (CIN * 4) + g4 * 16 : kOOB;
             wpos[k] = e < WPOS * 4 ? pos * 16 + g4 * 4 : -1;
             static_for<0, NCC>([&](auto ccc) {
                 constexpr int cc = decltype(ccc)::value;
@@ -755,18 +782,19 @@ __device__ __forceinline__ void uconv_body(const UArgs& a, int bid_in) {
 // The plain step kernel: one layer per launch.
 template <int MODE, int CIN, int COUT, int TM, int TN, int WN, int WK, int NCH, int S, int EPI, int DT, int KS = 1>
 __global__ __launch_bounds__(64 * WN * WK) __attribute__((amdgpu_waves_per_eu((WN * WK + 3) / 4, (WN * WK + 3) / 4)))
-void uconv_kernel(UArgs a) {
+void uconv_kernel(const float* w, const float* x, int32_t xbytes, uint32_t dec, int32_t tiles, int32_t Nq, int32_t Hin,
+                  int32_t Win, uint32_t mul_hw, uint32_t mul_w, uint32_t shr, UArgs a) {
+    const UHead h{w, x, xbytes, dec, tiles, Nq, Hin, Win, mul_hw, mul_w, shr};   // (see UHead: the preloaded parameters)
     if constexpr (KS == kTapClass) {
         // blocks [0, tiles): tap class 1, [tiles, 2 tiles): class 2 — the two blocks of a tile are a whole number of
         // XCD rounds apart (tile counts that are multiples of 8), so they read the tile's activations from one L2.
         // NCH / S are class 2's chunk counts (5 taps per channel chunk); class 1 runs 4 per channel chunk.
-        const int tiles = a.nMt * a.nNt;
-        if ((int)blockIdx.x < tiles)
-            uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH / 5 * 4, S / 5 * 4, EPI, DT, 1, 1>(a, blockIdx.x);
+        if ((int)blockIdx.x < h.tiles)
+            uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH / 5 * 4, S / 5 * 4, EPI, DT, 1, 1>(h, a, blockIdx.x);
         else
-            uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH, S, EPI, DT, 1, 2>(a, (int)blockIdx.x - tiles);
+            uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH, S, EPI, DT, 1, 2>(h, a, (int)blockIdx.x - h.tiles);
     } else {
-        uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH, S, EPI, DT, KS>(a, blockIdx.x);
+        uconv_body<MODE, CIN, COUT, TM, TN, WN, WK, NCH, S, EPI, DT, KS>(h, a, blockIdx.x);
     }
 }
 
@@ -799,6 +827,8 @@ static int set_grid(UArgs& a, const KsWs& k) {
         for (int pm = 1; pm <= 8; pm *= 2) {
             const int pn = 8 / pm;
             if (a.nMt % pm || a.nNt % pn) continue;
+            const int ml = a.nMt / pm;   // (the kernel decodes with shifts: whole powers of two, nNt / xpn in 24 bits)
+            if ((ml & (ml - 1)) != 0 || ml > (1 << 15) || a.nNt / pn >= (1 << 24)) continue;
             const int64_t est = pn * wbytes + pm * xbytes;
             if (best < 0 || est < best) best = est, a.xpm = pm, a.xpn = pn;
         }
@@ -815,6 +845,29 @@ static int set_grid(UArgs& a, const KsWs& k) {
         a.slab = k.ws + k.cnt_floats;
     }
     return 0;
+}
+
+// The head record of a launch from its finished arguments (make_args and set_grid have run).
+static inline UHead make_head(const UArgs& a, int cin) {
+    auto log2u = [](int v) {
+        uint32_t l = 0;
+        while ((1 << l) < v) ++l;
+        return l;
+    };
+    UHead h{};
+    h.w = a.w;
+    h.x = a.x;
+    h.xbytes = a.B * a.Hin * a.Win * cin * 4;
+    h.dec = (uint32_t)a.order;
+    if (a.order == 2) h.dec |= log2u(a.xpn) << 2 | log2u(a.nMt / a.xpm) << 4 | (uint32_t)(a.nNt / a.xpn) << 8;
+    h.tiles = a.nMt * a.nNt;
+    h.Nq = a.Nq;
+    h.Hin = a.Hin;
+    h.Win = a.Win;
+    h.mul_hw = a.fd_hw.mul;
+    h.mul_w = a.fd_w.mul;
+    h.shr = a.fd_hw.shr | (a.fd_hw.one & 1u) << 5 | a.fd_w.shr << 8 | (a.fd_w.one & 1u) << 13;
+    return h;
 }
 
 template <int MODE, int CIN, int COUT, int TM, int TN, int WN, int WK, int NCH, int S, int EPI, int DT, int KS>
@@ -839,7 +892,9 @@ static int launch_dt(const UArgs& a, hipStream_t st) {
             opted = true;
         }
     }
-    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(64 * WN * WK), lds, st, a);
+    const UHead h = make_head(a, CIN);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(64 * WN * WK), lds, st, h.w, h.x, h.xbytes, h.dec, h.tiles, h.Nq, h.Hin,
+                       h.Win, h.mul_hw, h.mul_w, h.shr, a);
     LDM_CHECK_LAUNCH("uconv_kernel");
     return 0;
 }

@@ -6,9 +6,12 @@ set -e
 cd "$(dirname "$0")/../music-style-transfer-ldm_amd/csrc"
 f=$1; shift
 D=$(echo $f | tr a-z A-Z)_DIAG
+# (the units the Makefile compiles with kernarg preload get it here too)
+P=""
+case " $(sed -n 's/^PRELOAD_SRCS := //p' Makefile) " in *" $f.hip "*) P="-mllvm -amdgpu-kernarg-preload-count=16";; esac
 for k in "$@"; do
   mkdir -p ../build/${f}d$k
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -D$D=$k -fno-gpu-rdc -x hip -c $f.hip -o ../build/${f}d$k/$f.hip.o &
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -D$D=$k -fno-gpu-rdc $P -x hip -c $f.hip -o ../build/${f}d$k/$f.hip.o &
 done
 wait
 others=""
