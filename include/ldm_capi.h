@@ -531,6 +531,9 @@ int ldm_u8_to_unit(const uint8_t* in, float* out, int64_t n, void* stream);
  * r_prev = r  from angles = init_angles [B, F, T] complex, then y [B, L] = istft(mag * angles); L must give T
  * frames.  Two launches per iteration on `stream`, no host synchronisation or allocation (capturable); workspace:
  * ldm_griffinlim_workspace(B, n_fft, T) floats.
+ * ldm_griffinlim_anchored: the same loop, workspace and launch sequence with the phase pulled towards anchor_phase
+ * [B, F, T] complex (unit modulus) by anchor_w [B, F, T] in [0, 1]: every iteration stores
+ * unit(a anchor_phase + (1 - a) angles): angles itself where a == 0, anchor_phase itself where a == 1 (bitwise).
  * ldm_mel_project: mel [B, n_mels, T] = M . P [B, F, T]; M [n_mels, F] dense, lohi [n_mels][2] each row's
  * non-zero run [lo, hi).
  * ldm_power_to_db: per item b of x [B, n]: 10 log10(max(x, amin)) - 10 log10(max(amin, max_b x)), clamped below at
@@ -547,6 +550,10 @@ int64_t ldm_griffinlim_workspace(int32_t B, int32_t n_fft, int32_t T);
 int ldm_griffinlim(const float* mag, const float* init_angles, float* y, int32_t B, int32_t T, int64_t L,
                    int32_t n_fft, int32_t hop, int32_t n_iter, float momentum, const float* tables,
                    float* workspace, void* stream);
+int ldm_griffinlim_anchored(const float* mag, const float* init_angles, const float* anchor_phase,
+                            const float* anchor_w, float* y, int32_t B, int32_t T, int64_t L, int32_t n_fft,
+                            int32_t hop, int32_t n_iter, float momentum, const float* tables, float* workspace,
+                            void* stream);
 int ldm_mel_project(const float* P, const float* M, const int32_t* lohi, float* mel, int32_t B, int32_t F,
                     int32_t n_mels, int32_t T, void* stream);
 int ldm_power_to_db(const float* x, float* out, int32_t B, int64_t n, float amin, float top_db, float* workspace,
@@ -555,6 +562,25 @@ int ldm_db_to_power(const float* x, float* out, int64_t n, void* stream);
 int ldm_mel_invert(const float* mel, const float* M, const float* Mt, const float* Minv, const int32_t* lohi,
                    float inv_lambda, int32_t iters, int32_t take_sqrt, float* x, float* workspace, int32_t B,
                    int32_t F, int32_t n_mels, int32_t T, void* stream);
+
+/* ---- content-anchored vocoder (vocoder.hip) ------------------------------------------------
+ * The transfer as an edit of the content's STFT C [B, F, T] complex.  mel_out, mel_content [B, n_mels, T] mel power
+ * (the content's after the same round trip as the output's); Wn [n_mels, F] the filterbank divided by its column
+ * sums (0 in a column whose sum is 0); mlohi [F][2] each bin's run [m_lo, m_hi) of filters with a non-zero weight
+ * (empty: the bin's gain is 1); eps [B] on the device, one positive floor per item.
+ *   g = clamp(sum_m Wn[m, f] (mel_out + eps) / (mel_content + eps), 0, max_gain),   Pm = g |C|^2
+ *   mag = sqrt(Pm + residual)   (residual [B, F, T] power, or null),   phase0 = C / |C|   ((1, 0) where |C| is below
+ *   the smallest normal fp32),   anchor = clamp(1 - |10 log10((mag^2 + eps) / (|C|^2 + eps))| / anchor_db, 0, 1)
+ *   (0 everywhere when anchor_db <= 0).
+ * ldm_mel_gain_power writes Pm, ldm_mel_gain_target writes mag, phase0 (complex) and anchor; one launch each, one
+ * lane per bin, no workspace, no host synchronisation (capturable). */
+int ldm_mel_gain_power(const float* C, const float* mel_out, const float* mel_content, const float* Wn,
+                       const int32_t* mlohi, const float* eps, float max_gain, float* Pm, int32_t B, int32_t F,
+                       int32_t n_mels, int32_t T, void* stream);
+int ldm_mel_gain_target(const float* C, const float* mel_out, const float* mel_content, const float* Wn,
+                        const int32_t* mlohi, const float* eps, float max_gain, float anchor_db,
+                        const float* residual, float* mag, float* phase0, float* anchor, int32_t B, int32_t F,
+                        int32_t n_mels, int32_t T, void* stream);
 
 /* ---- resampling and silence trim (resample.hip) -------------------------------------------
  * The rational polyphase resampler  y[n] = sum_{j=-W..W} x[i0 + j] * taps[p][j + W],  i0 = floor(n down / up),

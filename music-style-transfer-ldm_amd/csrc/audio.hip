@@ -20,6 +20,7 @@
 #include "mel_db.h"
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace ldm {
@@ -147,10 +148,21 @@ struct StftOut {
     float mom;         // momentum / (1 + momentum)
 };
 
+// The anchored Griffin-Lim epilogue's two extra operands: the phase the loop is pulled towards and
+// how strongly, per bin.
+struct StftOutAnchored : StftOut {
+    const float2* p0;   // [B, F, T] unit phase
+    const float* aw;    // [B, F, T] weight in [0, 1]
+};
+template <bool ANCHOR>
+using StftOutOf = std::conditional_t<ANCHOR, StftOutAnchored, StftOut>;
+
 // grid (ceil(T / 4), B).  y [B, L]; frame t covers y_padded[t hop, t hop + N), y_padded = reflect pad by N/2.
-template <int LOG2N>
+// ANCHOR: the Griffin-Lim epilogue stores unit(a p0 + (1 - a) angles) instead of angles: angles itself where a == 0
+// and p0 itself where a == 1, bitwise (p0 is read only where a > 0).
+template <int LOG2N, bool ANCHOR = false>
 __global__ __launch_bounds__(kThreads) void stft_kernel(const float* __restrict__ y, int64_t L, int T,
-                                                        const float* __restrict__ tables, StftOut o) {
+                                                        const float* __restrict__ tables, StftOutOf<ANCHOR> o) {
     using X = Geo<LOG2N>;
     constexpr int N = X::N, H = X::H, NT = X::NT, G = X::G, F = H + 1;
     __shared__ float s_re[G * H];
@@ -210,7 +222,21 @@ __global__ __launch_bounds__(kThreads) void stft_kernel(const float* __restrict_
             const float2 rp = o.r_prev[at];
             const float ax = v.x - o.mom * rp.x, ay = v.y - o.mom * rp.y;
             const float inv = 1.0f / (sqrtf(ax * ax + ay * ay) + kTiny);
-            o.angles[at] = make_float2(ax * inv, ay * inv);
+            float2 ang = make_float2(ax * inv, ay * inv);
+            if constexpr (ANCHOR) {
+                const float w = o.aw[at];
+                if (w > 0.f) {
+                    const float2 p = o.p0[at];
+                    if (w >= 1.f) {
+                        ang = p;
+                    } else {
+                        const float bx = w * p.x + (1.0f - w) * ang.x, by = w * p.y + (1.0f - w) * ang.y;
+                        const float binv = 1.0f / (sqrtf(bx * bx + by * by) + kTiny);
+                        ang = make_float2(bx * binv, by * binv);
+                    }
+                }
+            }
+            o.angles[at] = ang;
             o.r_prev[at] = v;
         }
     }
@@ -437,6 +463,17 @@ int launch_stft(const float* y, int B, int64_t L, int n_fft, int T, const float*
     return 0;
 }
 
+int launch_stft_anchored(const float* y, int B, int64_t L, int n_fft, int T, const float* tables, const StftOutAnchored& o,
+                         hipStream_t st) {
+    const dim3 grid((T + kFrames - 1) / kFrames, B);
+    if (n_fft == 2048)
+        hipLaunchKernelGGL((stft_kernel<11, true>), grid, dim3(kThreads), 0, st, y, L, T, tables, o);
+    else
+        hipLaunchKernelGGL((stft_kernel<9, true>), grid, dim3(kThreads), 0, st, y, L, T, tables, o);
+    LDM_CHECK_LAUNCH("stft_kernel<anchored>");
+    return 0;
+}
+
 int launch_istft(const float* S, const float* mag, float* y, int B, int T, int64_t L, int n_fft, const float* tables,
                  hipStream_t st) {
     const int hop = n_fft / 4;
@@ -453,6 +490,30 @@ int launch_istft(const float* S, const float* mag, float* y, int B, int T, int64
                            jbeg, jend, seg, tables);
     LDM_CHECK_LAUNCH("istft_kernel");
     return 0;
+}
+
+// The Griffin-Lim loop of ldm_griffinlim / ldm_griffinlim_anchored (p0 and aw null: the plain epilogue).
+int run_griffinlim(const float* mag, const float* init_angles, const float* p0, const float* aw, float* y, int B, int T,
+                   int64_t L, int n_fft, int n_iter, float momentum, const float* tables, float* workspace,
+                   hipStream_t st) {
+    const int64_t cplx = 2 * (int64_t)B * (n_fft / 2 + 1) * T;
+    float* r_prev = workspace;
+    float* angles = workspace + cplx;
+    LDM_HIP_TRY(hipMemsetAsync(r_prev, 0, sizeof(float) * cplx, st));
+    const float* cur = init_angles;
+    for (int it = 0; it < n_iter; ++it) {
+        if (int rc = launch_istft(cur, mag, y, B, T, L, n_fft, tables, st)) return rc;
+        StftOut o{nullptr, nullptr, 0, reinterpret_cast<float2*>(r_prev), reinterpret_cast<float2*>(angles),
+                  momentum / (1.0f + momentum)};
+        if (p0) {
+            StftOutAnchored oa{o, reinterpret_cast<const float2*>(p0), aw};
+            if (int rc = launch_stft_anchored(y, B, L, n_fft, T, tables, oa, st)) return rc;
+        } else {
+            if (int rc = launch_stft(y, B, L, n_fft, T, tables, o, st)) return rc;
+        }
+        cur = angles;
+    }
+    return launch_istft(cur, mag, y, B, T, L, n_fft, tables, st);
 }
 
 }  // namespace
@@ -521,20 +582,23 @@ extern "C" int ldm_griffinlim(const float* mag, const float* init_angles, float*
     LDM_REQUIRE(L >= n_fft / 2 + 1 && 1 + L / hop == T, "griffinlim: L must give T frames (1 + L / hop == T) and be "
                                                        ">= n_fft/2 + 1");
     LDM_REQUIRE(n_iter >= 0 && momentum >= 0.f, "griffinlim: n_iter and momentum must be non-negative");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t cplx = 2 * (int64_t)B * (n_fft / 2 + 1) * T;
-    float* r_prev = workspace;
-    float* angles = workspace + cplx;
-    LDM_HIP_TRY(hipMemsetAsync(r_prev, 0, sizeof(float) * cplx, st));
-    const float* cur = init_angles;
-    for (int it = 0; it < n_iter; ++it) {
-        if (int rc = launch_istft(cur, mag, y, B, T, L, n_fft, tables, st)) return rc;
-        StftOut o{nullptr, nullptr, 0, reinterpret_cast<float2*>(r_prev), reinterpret_cast<float2*>(angles),
-                  momentum / (1.0f + momentum)};
-        if (int rc = launch_stft(y, B, L, n_fft, T, tables, o, st)) return rc;
-        cur = angles;
-    }
-    return launch_istft(cur, mag, y, B, T, L, n_fft, tables, st);
+    return run_griffinlim(mag, init_angles, nullptr, nullptr, y, B, T, L, n_fft, n_iter, momentum, tables, workspace,
+                          (hipStream_t)stream);
+}
+
+extern "C" int ldm_griffinlim_anchored(const float* mag, const float* init_angles, const float* anchor_phase,
+                                       const float* anchor_w, float* y, int32_t B, int32_t T, int64_t L, int32_t n_fft,
+                                       int32_t hop, int32_t n_iter, float momentum, const float* tables,
+                                       float* workspace, void* stream) {
+    LDM_AUDIO_GEOMETRY("griffinlim_anchored", n_fft, hop);
+    LDM_REQUIRE(mag && init_angles && anchor_phase && anchor_w && y && tables && workspace,
+                "griffinlim_anchored: null pointer");
+    LDM_REQUIRE(B >= 1 && B <= 65535 && T >= 1, "griffinlim_anchored: B or T out of range");
+    LDM_REQUIRE(L >= n_fft / 2 + 1 && 1 + L / hop == T, "griffinlim_anchored: L must give T frames (1 + L / hop == T) "
+                                                       "and be >= n_fft/2 + 1");
+    LDM_REQUIRE(n_iter >= 0 && momentum >= 0.f, "griffinlim_anchored: n_iter and momentum must be non-negative");
+    return run_griffinlim(mag, init_angles, anchor_phase, anchor_w, y, B, T, L, n_fft, n_iter, momentum, tables,
+                          workspace, (hipStream_t)stream);
 }
 
 extern "C" int ldm_mel_project(const float* P, const float* M, const int32_t* lohi, float* mel, int32_t B, int32_t F,

@@ -142,6 +142,13 @@ SIGNATURES = {
     "ldm_db_to_power": (c_int32, [c_fp, c_fp, c_int64, c_vp]),
     "ldm_mel_invert": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_vp, c_float, c_int32, c_int32, c_fp, c_fp, c_int32,
                                  c_int32, c_int32, c_int32, c_vp]),
+    "ldm_griffinlim_anchored": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_int64, c_int32, c_int32,
+                                          c_int32, c_float, c_fp, c_fp, c_vp]),
+    # content-anchored vocoder (vocoder.hip)
+    "ldm_mel_gain_power": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_vp, c_fp, c_float, c_fp, c_int32, c_int32, c_int32,
+                                     c_int32, c_vp]),
+    "ldm_mel_gain_target": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_vp, c_fp, c_float, c_float, c_fp, c_fp, c_fp, c_fp,
+                                      c_int32, c_int32, c_int32, c_int32, c_vp]),
     # resampling and silence trim (resample.hip)
     "ldm_resample_out_len": (c_int64, [c_int64, c_int32, c_int32]),
     "ldm_resample_f32": (c_int32, [c_fp, c_int32, c_int64, c_fp, c_int32, c_int32, c_int32, c_fp, c_vp]),

@@ -157,10 +157,17 @@ def random_phase(shape, seed=None, device="cuda"):
     return torch.complex(torch.cos(u), torch.sin(u))
 
 
-def griffinlim(mag, n_iter=32, momentum=0.99, seed=None, length=None, n_fft=None, hop_length=None, init_phase=None):
+def griffinlim(mag, n_iter=32, momentum=0.99, seed=None, length=None, n_fft=None, hop_length=None, init_phase=None,
+               anchor_phase=None, anchor=None):
     """Fast Griffin-Lim (librosa's recurrence) on |STFT| mag [B, F, T]: y [B, length]; length defaults to
     (T - 1) * hop and must give T frames.  The initial phase is init_phase [B, F, T] complex64 when given, else
-    drawn from a generator seeded with `seed`."""
+    drawn from a generator seeded with `seed`.
+
+    anchor_phase [B, F, T] complex64 (unit modulus) with anchor [B, F, T] in [0, 1], both or neither: every
+    iteration's phase becomes unit(a anchor_phase + (1 - a) angles): the plain recurrence where a == 0, anchor_phase
+    held where a == 1.  Neither: the call it always was."""
+    if (anchor_phase is None) != (anchor is None):
+        raise ValueError("griffinlim: anchor_phase and anchor go together (both or neither)")
     mag, one = _batched(mag, 3)
     mag = ops.f32c(mag)
     n_fft = 2 * (mag.shape[-2] - 1) if n_fft is None else n_fft
@@ -170,13 +177,135 @@ def griffinlim(mag, n_iter=32, momentum=0.99, seed=None, length=None, n_fft=None
         init_phase = random_phase(mag.shape, seed, mag.device)
     elif init_phase.dim() == 2:
         init_phase = init_phase.unsqueeze(0)
-    y = ops.griffinlim(mag, init_phase, n_iter, momentum, length, n_fft, hop)
+    if anchor is not None:
+        anchor_phase, anchor = _batched(anchor_phase, 3)[0], ops.f32c(_batched(anchor, 3)[0])
+    y = ops.griffinlim(mag, init_phase, n_iter, momentum, length, n_fft, hop, anchor_phase, anchor)
     return y[0] if one else y
 
 
 def mel_to_audio(mel, sr=SR, n_fft=N_FFT, n_iter=32, nnls_iters=32, momentum=0.99, seed=None, length=None):
     """Waveform [B, (T - 1) * hop] of a mel power spectrogram [B, n_mels, T]: mel_to_stft, then griffinlim."""
     return griffinlim(mel_to_stft(mel, sr, n_fft, nnls_iters), n_iter, momentum, seed, length, n_fft)
+
+
+# ---- content-anchored vocoder (csrc/vocoder.hip; DESIGN.md §7k) ----------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _gain_host(sr, n_fft, n_mels):
+    """(Wn fp32 [n_mels, F], mlohi int32 [F, 2]): the filterbank divided by its column sums (a column no filter covers
+    stays 0) and each bin's run [m_lo, m_hi) of filters with a non-zero weight, the transpose of _mel_host's lohi."""
+    M = mel_filterbank(sr, n_fft, n_mels)
+    col = M.sum(axis=0)
+    Wn = np.divide(M, col[None, :], out=np.zeros_like(M), where=col[None, :] > 0)
+    mlohi = np.zeros((M.shape[1], 2), dtype=np.int32)
+    for f in range(M.shape[1]):
+        nz = np.flatnonzero(M[:, f])
+        if nz.size:
+            mlohi[f] = (nz[0], nz[-1] + 1)
+    return Wn.astype(np.float32), mlohi
+
+
+_GAIN_DEV = {}
+
+
+def _gain_device(sr, n_fft, n_mels, device):
+    key = (sr, n_fft, n_mels, torch.device(device).index)
+    v = _GAIN_DEV.get(key)
+    if v is None:
+        v = _GAIN_DEV[key] = tuple(torch.from_numpy(a).to(device) for a in _gain_host(sr, n_fft, n_mels))
+    return v
+
+
+def check_vocoder_args(max_gain_db, anchor_db, what="mel_gain_target"):
+    """ValueError for a non-finite or negative max_gain_db or a non-finite anchor_db."""
+    if not math.isfinite(float(max_gain_db)) or float(max_gain_db) < 0:
+        raise ValueError(f"{what}: max_gain_db must be finite and non-negative, got {max_gain_db}")
+    if not math.isfinite(float(anchor_db)):
+        raise ValueError(f"{what}: anchor_db must be finite, got {anchor_db}")
+
+
+def _eps_device(eps, B, device, what):
+    """eps as float32 [B] on the device: a positive number, or one per item (a device tensor is taken as it is)."""
+    if torch.is_tensor(eps) and eps.is_cuda:
+        e = ops.f32c(eps).reshape(-1)
+    else:
+        e = torch.as_tensor(eps, dtype=torch.float64).reshape(-1)
+        if not bool(torch.isfinite(e).all()) or bool((e <= 0).any()):
+            raise ValueError(f"{what}: eps must be positive and finite, got {eps}")
+        e = e.to(torch.float32).to(device)
+    if e.numel() == 1 and B != 1:
+        e = e.expand(B).contiguous()
+    if e.numel() != B:
+        raise ValueError(f"{what}: eps must be one number or one per item ({B}), got {e.numel()}")
+    return e
+
+
+def _gain_inputs(what, C, mel_out, mel_content, eps, max_gain_db, anchor_db, sr):
+    check_vocoder_args(max_gain_db, anchor_db, what)
+    C, one = _batched(C, 3)
+    mel_out, mel_content = ops.f32c(_batched(mel_out, 3)[0]), ops.f32c(_batched(mel_content, 3)[0])
+    n_fft = 2 * (C.shape[-2] - 1)
+    Wn, mlohi = _gain_device(sr, n_fft, mel_out.shape[-2], C.device)
+    e = _eps_device(eps, C.shape[0], C.device, what)
+    return C, mel_out, mel_content, Wn, mlohi, e, 10.0 ** (float(max_gain_db) / 10.0), one
+
+
+def mel_gain_power(C, mel_out, mel_content, eps, max_gain_db=40.0, sr=SR):
+    """The content's power under the transfer's gain, Pm = g |C|^2 [B, F, T] (see mel_gain_target)."""
+    C, mel_out, mel_content, Wn, mlohi, e, mg, one = _gain_inputs("mel_gain_power", C, mel_out, mel_content, eps,
+                                                                  max_gain_db, 0.0, sr)
+    Pm = ops.mel_gain_power(C, mel_out, mel_content, Wn, mlohi, e, mg)
+    return Pm[0] if one else Pm
+
+
+def mel_gain_target(C, mel_out, mel_content, eps, max_gain_db=40.0, anchor_db=6.0, residual=None, sr=SR):
+    """The transfer as an edit of the content's STFT C [B, F, T] complex64 -> (mag, phase0, anchor), each [B, F, T].
+    mel_out, mel_content [B, n_mels, T] mel power: the output's and the content's after the same round trip; eps: a
+    positive floor, one number or one per item.  G = (mel_out + eps) / (mel_content + eps) is carried to the bins by
+    the filterbank normalised per bin, g = clamp(sum_m Wn[m, f] G[m, t], 0, 10^(max_gain_db / 10)) (1 where no filter
+    covers the bin), and mag = sqrt(g |C|^2 + residual), phase0 = C / |C| ((1, 0) where C vanishes), anchor =
+    clamp(1 - |10 log10((mag^2 + eps) / (|C|^2 + eps))| / anchor_db, 0, 1), 0 everywhere when anchor_db <= 0.
+    residual [B, F, T]: power added to the masked power (None: 0).  Where the mel did not change mag is |C| and anchor 1."""
+    C, mel_out, mel_content, Wn, mlohi, e, mg, one = _gain_inputs("mel_gain_target", C, mel_out, mel_content, eps,
+                                                                  max_gain_db, anchor_db, sr)
+    if residual is not None:
+        residual = ops.f32c(_batched(residual, 3)[0])
+    out = ops.mel_gain_target(C, mel_out, mel_content, Wn, mlohi, e, mg, anchor_db, residual)
+    return tuple(t[0] for t in out) if one else out
+
+
+def mel_to_audio_content(mel_out, content_wave, mel_content=None, sr=SR, n_fft=N_FFT, n_iter=32, momentum=0.99,
+                         max_gain_db=40.0, anchor_db=6.0, residual=True, nnls_iters=32, max_db=80, length=None):
+    """Waveform [B, length] of the mel power mel_out [B, n_mels, T] read as an edit of content_wave [B, L] (T = 1 +
+    L // hop): the content's STFT scaled by the mel-domain gain (mel_gain_target), then Griffin-Lim started from the
+    content's phase and anchored to it where the gain is near unity.  mel_content: the content's mel after the same
+    round trip as mel_out (None: melspectrogram(content_wave)); eps = max(mel_content) 10^(-max_db / 10) per item.
+    residual: add R = mel_to_stft(max((mel_out - mel_content) - (M Pm - M |C|^2), 0), sqrt=False), the energy a gain
+    cannot create: max(mel_out - M Pm, 0) when mel_content is the content's plain mel M |C|^2.
+    length defaults to (T - 1) * hop.  mel_out == mel_content returns istft(stft(content_wave))."""
+    check_vocoder_args(max_gain_db, anchor_db, "mel_to_audio_content")
+    y, one = _batched(content_wave, 2)
+    mel_out = ops.f32c(_batched(mel_out, 3)[0])
+    n_mels = mel_out.shape[-2]
+    M, _, _, lohi, _ = _mel_device(sr, n_fft, n_mels, y.device)
+    C, P = ops.stft(y, n_fft, None, "both")
+    mel_plain = ops.mel_project(P, M, lohi)
+    mel_content = mel_plain if mel_content is None else ops.f32c(_batched(mel_content, 3)[0])
+    if mel_out.shape != mel_content.shape or mel_out.shape[0] != C.shape[0] or mel_out.shape[-1] != C.shape[-1]:
+        raise ValueError(f"mel_to_audio_content: mel_out {tuple(mel_out.shape)}, mel_content "
+                         f"{tuple(mel_content.shape)} and the content's {C.shape[-1]} frames ({C.shape[0]} items) do "
+                         "not match")
+    tiny = float(np.finfo(np.float32).tiny)
+    eps = (mel_content.amax(dim=(1, 2)) * 10.0 ** (-float(max_db) / 10.0)).clamp_min(tiny)
+    R = None
+    if residual:
+        Pm = mel_gain_power(C, mel_out, mel_content, eps, max_gain_db, sr)
+        # what the output gained over the content, less what the gain delivered: both differences are taken within
+        # one representation, so the round trip's own error (mel_content against M |C|^2) is not read as added energy
+        D = ((mel_out - mel_content) - (ops.mel_project(Pm, M, lohi) - mel_plain)).clamp_min(0.0)
+        R = mel_to_stft(D, sr, n_fft, nnls_iters, sqrt=False)
+    mag, phase0, anchor = mel_gain_target(C, mel_out, mel_content, eps, max_gain_db, anchor_db, R, sr)
+    out = griffinlim(mag, n_iter, momentum, None, length, n_fft, None, phase0, phase0, anchor)
+    return out[0] if one else out
 
 
 # ---- resampling, silence trim, chunk images (csrc/resample.hip; DESIGN.md §7b) -------------------------------

@@ -1138,6 +1138,12 @@ def stft(y, n_fft=2048, hop_length=None, out="complex"):
         S = torch.empty((B, F, T), device=y.device, dtype=torch.complex64)
         L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), S.data_ptr(), None, 0, stream_handle())
         return S
+    if out == "both":      # (S, |S|^2) from one launch
+        S = torch.empty((B, F, T), device=y.device, dtype=torch.complex64)
+        P = torch.empty((B, F, T), device=y.device, dtype=torch.float32)
+        L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), S.data_ptr(), P.data_ptr(), 2,
+               stream_handle())
+        return S, P
     mag = torch.empty((B, F, T), device=y.device, dtype=torch.float32)
     L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), None, mag.data_ptr(),
            {"mag": 1, "power": 2}[out], stream_handle())
@@ -1163,8 +1169,10 @@ def istft(S, length=None, n_fft=2048, hop_length=None, mag=None):
     return y
 
 
-def griffinlim(mag, init_angles, n_iter, momentum, length, n_fft, hop_length=None):
-    """The Griffin-Lim loop (ldm_griffinlim) from init_angles [B, F, T] complex64; returns y [B, length]."""
+def griffinlim(mag, init_angles, n_iter, momentum, length, n_fft, hop_length=None, anchor_phase=None, anchor=None):
+    """The Griffin-Lim loop (ldm_griffinlim) from init_angles [B, F, T] complex64; returns y [B, length].  With
+    anchor_phase [B, F, T] complex64 and anchor [B, F, T] in [0, 1] (both or neither) the anchored loop
+    (ldm_griffinlim_anchored)."""
     require_device(mag, what="griffinlim")
     require_device(init_angles, dtype=torch.complex64, what="griffinlim")
     mag, init_angles = mag.contiguous(), init_angles.contiguous()
@@ -1172,10 +1180,24 @@ def griffinlim(mag, init_angles, n_iter, momentum, length, n_fft, hop_length=Non
     hop = n_fft // 4 if hop_length is None else int(hop_length)
     if F != n_fft // 2 + 1 or tuple(init_angles.shape) != (B, F, T):
         raise RuntimeError("griffinlim: mag / init_angles shapes do not match n_fft")
+    if (anchor_phase is None) != (anchor is None):
+        raise ValueError("griffinlim: anchor_phase and anchor go together (both or neither)")
+    if anchor is not None:
+        require_device(anchor, what="griffinlim")
+        require_device(anchor_phase, dtype=torch.complex64, what="griffinlim")
+        if tuple(anchor_phase.shape) != (B, F, T) or tuple(anchor.shape) != (B, F, T):
+            raise ValueError(f"griffinlim: anchor_phase {tuple(anchor_phase.shape)} and anchor {tuple(anchor.shape)} "
+                             f"must have mag's shape {(B, F, T)}")
+        anchor_phase, anchor = anchor_phase.contiguous(), anchor.contiguous()
     tab = stft_tables(n_fft, mag.device) if n_fft in (512, 2048) else mag
     ws = torch.empty(max(int(L.load().ldm_griffinlim_workspace(B, n_fft, T)), 1), device=mag.device,
                      dtype=torch.float32)
     y = torch.empty((B, int(length)), device=mag.device, dtype=torch.float32)
+    if anchor is not None:
+        L.call("ldm_griffinlim_anchored", mag.data_ptr(), init_angles.data_ptr(), anchor_phase.data_ptr(),
+               anchor.data_ptr(), y.data_ptr(), B, T, int(length), n_fft, hop, int(n_iter), float(momentum),
+               tab.data_ptr(), ws.data_ptr(), stream_handle())
+        return y
     L.call("ldm_griffinlim", mag.data_ptr(), init_angles.data_ptr(), y.data_ptr(), B, T, int(length), n_fft, hop,
            int(n_iter), float(momentum), tab.data_ptr(), ws.data_ptr(), stream_handle())
     return y
@@ -1224,6 +1246,52 @@ def mel_invert(mel, M, Mt, Minv, lohi, inv_lambda, iters, take_sqrt=True):
            float(inv_lambda), int(iters), int(bool(take_sqrt)), x.data_ptr(), ws.data_ptr(), B, F, n_mels, T,
            stream_handle())
     return x
+
+
+# ---- content-anchored vocoder (vocoder.hip) --------------------------------------------------
+def _gain_operands(name, C, mel_out, mel_content, Wn, mlohi, eps):
+    require_device(C, dtype=torch.complex64, what=name)
+    require_device(mel_out, mel_content, Wn, eps, what=name)
+    require_device(mlohi, dtype=torch.int32, what=name)
+    if C.dim() != 3 or mel_out.dim() != 3:
+        raise ValueError(f"{name}: C must be [B, F, T] and the mels [B, n_mels, T], got {tuple(C.shape)} and "
+                         f"{tuple(mel_out.shape)}")
+    B, F, T = C.shape
+    n_mels = mel_out.shape[1]
+    if tuple(mel_out.shape) != (B, n_mels, T) or tuple(mel_content.shape) != (B, n_mels, T):
+        raise ValueError(f"{name}: mel_out {tuple(mel_out.shape)} and mel_content {tuple(mel_content.shape)} must both "
+                         f"be [{B}, n_mels, {T}] (C is {tuple(C.shape)})")
+    if tuple(Wn.shape) != (n_mels, F) or tuple(mlohi.shape) != (F, 2) or tuple(eps.shape) != (B,):
+        raise ValueError(f"{name}: Wn must be [{n_mels}, {F}], mlohi [{F}, 2] and eps [{B}]")
+    return B, F, n_mels, T
+
+
+def mel_gain_power(C, mel_out, mel_content, Wn, mlohi, eps, max_gain):
+    """Pm [B, F, T] = g |C|^2 of ldm_mel_gain_power; eps [B] on the device, max_gain linear."""
+    B, F, n_mels, T = _gain_operands("mel_gain_power", C, mel_out, mel_content, Wn, mlohi, eps)
+    C, mel_out, mel_content, Wn, mlohi, eps = (t.contiguous() for t in (C, mel_out, mel_content, Wn, mlohi, eps))
+    Pm = torch.empty((B, F, T), device=C.device, dtype=torch.float32)
+    L.call("ldm_mel_gain_power", C.data_ptr(), mel_out.data_ptr(), mel_content.data_ptr(), Wn.data_ptr(),
+           mlohi.data_ptr(), eps.data_ptr(), float(max_gain), Pm.data_ptr(), B, F, n_mels, T, stream_handle())
+    return Pm
+
+
+def mel_gain_target(C, mel_out, mel_content, Wn, mlohi, eps, max_gain, anchor_db, residual=None):
+    """(mag [B, F, T], phase0 [B, F, T] complex64, anchor [B, F, T]) of ldm_mel_gain_target."""
+    B, F, n_mels, T = _gain_operands("mel_gain_target", C, mel_out, mel_content, Wn, mlohi, eps)
+    C, mel_out, mel_content, Wn, mlohi, eps = (t.contiguous() for t in (C, mel_out, mel_content, Wn, mlohi, eps))
+    if residual is not None:
+        require_device(residual, what="mel_gain_target")
+        if tuple(residual.shape) != (B, F, T):
+            raise ValueError(f"mel_gain_target: residual {tuple(residual.shape)} must have C's shape {(B, F, T)}")
+        residual = residual.contiguous()
+    mag = torch.empty((B, F, T), device=C.device, dtype=torch.float32)
+    phase0 = torch.empty((B, F, T), device=C.device, dtype=torch.complex64)
+    anchor = torch.empty((B, F, T), device=C.device, dtype=torch.float32)
+    L.call("ldm_mel_gain_target", C.data_ptr(), mel_out.data_ptr(), mel_content.data_ptr(), Wn.data_ptr(),
+           mlohi.data_ptr(), eps.data_ptr(), float(max_gain), float(anchor_db), _p(residual), mag.data_ptr(),
+           phase0.data_ptr(), anchor.data_ptr(), B, F, n_mels, T, stream_handle())
+    return mag, phase0, anchor
 
 
 # ---- whole-recording windows (longform.hip; DESIGN.md §7c) --------------------------------------------------

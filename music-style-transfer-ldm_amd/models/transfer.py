@@ -8,6 +8,7 @@ are crossfaded into one mel spectrogram that is vocoded once, so the phase is co
     python -m models.transfer --content a.wav --style b.wav c.wav --solver dpmpp2m --style-morph --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --keep-band 0:200 --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --joint --batch 16 --out o.wav
+    python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --vocoder content --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
 """
@@ -37,7 +38,8 @@ def style_window_indices(Ns, refs):
 def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, num_timesteps=100, eta=0.0,
                        batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None,
                        style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None, keep=None,
-                       composite=True, style_map=None, joint=False):
+                       composite=True, style_map=None, joint=False, vocoder="griffinlim", max_gain_db=40.0,
+                       anchor_db=6.0, residual=True):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -83,8 +85,20 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     two decodings of the same latent instead of two independent samples.  The seam between two groups is not fused
     (its windows only share the canvas noise): batch_size >= N gives one coherent canvas.  Beyond 8 windows per call
     the sampler's bottleneck runs without its value fold (slower per window, the same results up to rounding).
-    Composes with mixing, guidance, keep and the style map.  joint=False is the call it always was."""
+    Composes with mixing, guidance, keep and the style map.  joint=False is the call it always was.
+
+    Vocoder: "griffinlim" (the default, the call it always was) inverts the stitched mel (audio.mel_to_audio: NNLS,
+    then Griffin-Lim from a random phase seeded with `seed`).  "content" reads the result as an edit of the content's
+    own STFT (audio.mel_to_audio_content): the content's magnitudes scaled by the mel-domain gain
+    between the stitched output and the content's mel after the same window / dB clip / crossfade round trip
+    (clamped at max_gain_db), plus, with residual, the energy the style adds where the content has none; n_iter
+    iterations of Griffin-Lim start from the content's phase and stay anchored to it where the gain is within
+    anchor_db of unity (anchor_db <= 0: no anchor), so an untouched or composited region comes back as the content
+    itself.  `seed` plays no part in it.  Works with every solver and with solver=None."""
     n_mels = 128
+    if vocoder not in ("griffinlim", "content"):
+        raise ValueError(f"transfer_recording: vocoder must be \"griffinlim\" or \"content\", got {vocoder!r}")
+    audio.check_vocoder_args(max_gain_db, anchor_db, "transfer_recording")
     if joint:
         if solver is None:
             raise ValueError("transfer_recording: joint needs a solver (the reference's sampler has no seam fuse)")
@@ -165,6 +179,11 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     Ns = max(1, Ps.shape[-1] // frames)       # the full windows; a style shorter than one keeps its padded window
     xs = xs[:Ns]
 
+    voc = None
+    if vocoder == "content":
+        voc = dict(content=content, x=x, max_gain_db=float(max_gain_db), anchor_db=float(anchor_db),
+                   residual=bool(residual))
+
     latent = model.unet.enc1.weight.shape[1]
     if joint:
         noise = longform.noise_windows(N, latent, n_mels // 8, frames // 8, overlap // 8, seed)
@@ -223,7 +242,7 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                                                               solver=solver, eta=eta, noise=noise[b0:b1],
                                                               style_weights=wb, **guide_kw(b0, b1))
                 out.append(decoded)
-        return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N)
+        return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N, voc)
     pair = torch.arange(N, device=content.device) % Ns
     out = []
     with torch.no_grad():
@@ -238,13 +257,21 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                                                           steps=num_timesteps, solver=solver, eta=eta,
                                                           noise=noise[b0:b1], **guide_kw(b0, b1))
             out.append(decoded)
-    return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N)
+    return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N, voc)
 
 
-def _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N):
+def _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N, voc=None):
     windows_out = torch.cat(out)
     mel_power = longform.stitch_windows(windows_out, ref_db, overlap, T_total, max_db)
-    y = audio.mel_to_audio(mel_power, sr=sr, n_iter=n_iter, nnls_iters=nnls_iters, seed=seed, length=Ln)
+    if voc is None:
+        y = audio.mel_to_audio(mel_power, sr=sr, n_iter=n_iter, nnls_iters=nnls_iters, seed=seed, length=Ln)
+    else:
+        # the content's mel through the windows, the dB clip and the crossfade the output went through: G = 1 wherever
+        # a decoded window is the content window
+        mel_content = longform.stitch_windows(voc["x"], ref_db, overlap, T_total, max_db)
+        y = audio.mel_to_audio_content(mel_power, voc["content"], mel_content, sr=sr, n_iter=n_iter,
+                                       max_gain_db=voc["max_gain_db"], anchor_db=voc["anchor_db"],
+                                       residual=voc["residual"], nnls_iters=nnls_iters, max_db=max_db, length=Ln)
     return SimpleNamespace(audio=y, mel_power=mel_power, windows_out=windows_out, ref_db=ref_db, N=N)
 
 
@@ -317,6 +344,17 @@ def parse_args(argv=None):
                    help="denoise the windows of a model call as one latent canvas (needs --solver and an --overlap "
                         "that is a multiple of 8): the columns neighbouring windows share are fused after every step; "
                         "--batch at least the window count gives one coherent canvas")
+    p.add_argument("--vocoder", choices=("griffinlim", "content"), default="griffinlim",
+                   help="how the stitched mel becomes audio: \"griffinlim\" inverts it from a random phase; "
+                        "\"content\" edits the content's own STFT (its magnitudes times the mel-domain gain, its "
+                        "phase kept where little changed), so untouched regions come back as they went in")
+    p.add_argument("--max-gain-db", type=float, default=40.0, dest="max_gain_db",
+                   help="--vocoder content: the most a bin's power may be raised, in dB")
+    p.add_argument("--anchor-db", type=float, default=6.0, dest="anchor_db",
+                   help="--vocoder content: bins whose power changes by less than this many dB keep (part of) the "
+                        "content's phase; 0 or less anchors nothing")
+    p.add_argument("--no-residual", action="store_false", dest="residual",
+                   help="--vocoder content: do not add the energy the style puts where the content is silent")
     p.add_argument("--batch", type=int, default=8, help="windows per model call")
     p.add_argument("--seed", type=int, default=0)
     args = p.parse_args(argv)
@@ -334,6 +372,10 @@ def parse_args(argv=None):
         p.error("--keep-time / --keep-band need --solver")
     if args.keep_feather < 0:
         p.error("--keep-feather must not be negative")
+    if not math.isfinite(args.max_gain_db) or args.max_gain_db < 0:
+        p.error("--max-gain-db must be finite and non-negative")
+    if not math.isfinite(args.anchor_db):
+        p.error("--anchor-db must be finite")
     if args.joint and args.solver is None:
         p.error("--joint needs --solver")
     if args.joint and args.overlap % 8:
@@ -367,6 +409,9 @@ def main(argv=None):
         guide["style_map"] = longform.morph_map(len(styles), 1 + content.numel() // HOP)
     if args.joint:
         guide["joint"] = True
+    if args.vocoder != "griffinlim":      # (without the flag: today's call)
+        guide.update(vocoder=args.vocoder, max_gain_db=args.max_gain_db, anchor_db=args.anchor_db,
+                     residual=args.residual)
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
                              num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
                              solver=args.solver, t_start=args.t_start, style_weights=args.style_weights,
