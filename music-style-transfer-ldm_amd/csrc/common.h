@@ -282,9 +282,9 @@ struct StepConv {
 int step_conv(int layer, int B, int H, int W, const StepConv& s, hipStream_t st);
 int64_t step_ws_floats(int B, int H, int W, int64_t* cnt_floats = nullptr);
 int step_ks_mask();   // layers running the K-split step form (LDM_UCONV_KS)
-// LDM_DEBUG_BOUNDS (make DIAG=1: the diagnostic library lib/libldm_amd_diag.so): the multi-tensor optimizer kernels check the chunk map they
+// LDM_DEBUG_BOUNDS (make DIAG=1: the diagnostic library lib/libldm_amd_diag.so): the multi-tensor optimizer kernels (optim.hip, chunk_open) check the chunk map they
 // index the slot table with (chunk_tensor[i] in [0, nchunks), chunk_start >= 0, a non-null gradient) and print
-// and skip a bad chunk instead of dereferencing it (round 5's aperture violation in unscale_check_kernel read
+// and skip a bad chunk instead of dereferencing it (round 5's aperture violation in unscale_check_kernel<false> read
 // a slot table that the graph's own scratch had overwritten)
 #ifndef LDM_DEBUG_BOUNDS
 #define LDM_DEBUG_BOUNDS 0

@@ -97,6 +97,10 @@ class _SlotTable:
     def __init__(self, *args):
         pass
 
+    def args(self):
+        """The five leading arguments of every multi-tensor entry: slots, chunk map, chunk count, chunk length."""
+        return (self.slots.data_ptr(), self.chunk_tensor.data_ptr(), self.chunk_start.data_ptr(), self.nchunks, CHUNK)
+
 
 def reserve_capture_buffers(n=4, words=1 << 14, device="cuda"):
     """Pinned host buffers and device buffers for the slot tables built while a step is being captured into
@@ -149,8 +153,7 @@ def scale_tensors_(tensors, factor):
     tab = _SlotTable(tensors, tensors, [None] * len(tensors), [None] * len(tensors))
     f = torch.full((1,), float(factor), dtype=torch.float32, device=tensors[0].device)
     bad = torch.zeros((1,), dtype=torch.int32, device=tensors[0].device)
-    L.call("ldm_unscale_check", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-           tab.nchunks, CHUNK, f.data_ptr(), bad.data_ptr(), stream_handle())
+    L.call("ldm_unscale_check", *tab.args(), f.data_ptr(), bad.data_ptr(), stream_handle())
     return bad
 
 
@@ -193,9 +196,8 @@ def _norm_pass(groups, max_norm, inv_scale, cache, found_inf=None):
     flag = buf.found_inf if found_inf is None else found_inf
     off = 0
     for tab in tabs:
-        L.call("ldm_unscale_check_norm", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-               tab.nchunks, CHUNK, None if inv_scale is None else inv_scale.data_ptr(), flag.data_ptr(),
-               buf.partials.data_ptr() + 8 * off, stream_handle())
+        L.call("ldm_unscale_check_norm", *tab.args(), None if inv_scale is None else inv_scale.data_ptr(),
+               flag.data_ptr(), buf.partials.data_ptr() + 8 * off, stream_handle())
         off += tab.nchunks
     L.call("ldm_grad_norm_finalize", buf.partials.data_ptr(), buf.nchunks, float(max_norm), buf.pair.data_ptr(),
            stream_handle())
@@ -234,8 +236,7 @@ def clip_grad_norm_(parameters, max_norm):
         raise ValueError("ldm_amd.optim.clip_grad_norm_: no parameter has a gradient")
     buf, tabs = _norm_pass([ps], max_norm, None, _norm_cache)
     tab = tabs[0]
-    L.call("ldm_unscale_check", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-           tab.nchunks, CHUNK, buf.pair.data_ptr() + 4, buf.found_inf.data_ptr(), stream_handle())
+    L.call("ldm_unscale_check", *tab.args(), buf.pair.data_ptr() + 4, buf.found_inf.data_ptr(), stream_handle())
     buf.tabs = tabs
     return buf.pair[0].clone()
 
@@ -250,8 +251,8 @@ def ema_update_(ema_tensors, sources, decay, found_inf=None):
     es, ss = [e for e, _ in pairs], [s for _, s in pairs]
     require_device(*es, *ss, what="ema_update_")
     tab = _SlotTable(es, ss, [None] * len(es), [None] * len(es))
-    L.call("ldm_ema_update", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-           tab.nchunks, CHUNK, float(decay), None if found_inf is None else found_inf.data_ptr(), stream_handle())
+    L.call("ldm_ema_update", *tab.args(), float(decay), None if found_inf is None else found_inf.data_ptr(),
+           stream_handle())
     return tab
 
 
@@ -372,6 +373,19 @@ class Adam(torch.optim.Optimizer):
             ext.ema_decay = self.ema_decay
         return ext
 
+    def _launch(self, tab, ps, group, found_inf, grad_mul, step, scalars=None):
+        """The Adam launch over `tab`, the table of `ps`.  step: the host step count, or with `scalars` (the
+        capturable form) the device step count's address.  The plain entry unless _ext gives a record."""
+        beta1, beta2 = group["betas"]
+        ext = self._ext(ps, grad_mul)
+        name = "ldm_adam_step" + ("" if scalars is None else "_dev") + ("" if ext is None else "_ext")
+        tail = () if scalars is None else (scalars.data_ptr(),)
+        if ext is not None:
+            tail += (ctypes.byref(ext),)
+        L.call(name, *tab.args(), float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
+               float(group["weight_decay"]), self._decoupled, step,
+               None if found_inf is None else found_inf.data_ptr(), *tail, stream_handle())
+
     @torch.no_grad()
     def step(self, closure=None, found_inf=None, grad_mul=None):
         """One Adam update.  found_inf (device int32 [1], optional): skip on the device if set.  grad_mul (device
@@ -386,9 +400,8 @@ class Adam(torch.optim.Optimizer):
             if not params:
                 continue
             _check_params(params)
-            beta1, beta2 = group["betas"]
             if self.capturable:
-                self._step_capturable(gi, group, params, found_inf, beta1, beta2, grad_mul)
+                self._step_capturable(gi, group, params, found_inf, grad_mul)
                 continue
             if "_ldm_step" in group:
                 # leaving the capturable form: every param gets its own host step count again (the shared
@@ -408,15 +421,7 @@ class Adam(torch.optim.Optimizer):
                 grads = [p.grad for p in ps]
                 tab = _SlotTable(ps, grads, [self.state[p]["exp_avg"] for p in ps],
                                  [self.state[p]["exp_avg_sq"] for p in ps])
-                ext = self._ext(ps, grad_mul)
-                args = (tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-                        tab.nchunks, CHUNK, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                        float(group["weight_decay"]), self._decoupled, step,
-                        None if found_inf is None else found_inf.data_ptr())
-                if ext is None:
-                    L.call("ldm_adam_step", *args, stream_handle())
-                else:
-                    L.call("ldm_adam_step_ext", *args, ctypes.byref(ext), stream_handle())
+                self._launch(tab, ps, group, found_inf, grad_mul, step)
                 # the tables are read by the kernel asynchronously: keep them alive until it ran
                 self._tables[(gi, step)] = tab
                 # the kernel wrote the parameters through raw pointers: move their autograd versions the
@@ -471,7 +476,7 @@ class Adam(torch.optim.Optimizer):
         # a captured train step holds the old state tensors: LDMTrainer re-captures when this moves
         self.state_epoch = getattr(self, "state_epoch", 0) + 1
 
-    def _step_capturable(self, gi, group, params, found_inf, beta1, beta2, grad_mul=None):
+    def _step_capturable(self, gi, group, params, found_inf, grad_mul=None):
         """One launch pair for the group: ldm_adam_step_dev advances the group's device step count (shared
         by its params' state["step"]) unless found_inf is set and forms the scalars from it on the device."""
         dev = params[0].device
@@ -492,15 +497,7 @@ class Adam(torch.optim.Optimizer):
             st["step"] = gstep
         tab = _SlotTable(params, [p.grad for p in params], [self.state[p]["exp_avg"] for p in params],
                          [self.state[p]["exp_avg_sq"] for p in params])
-        ext = self._ext(params, grad_mul)
-        args = (tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-                tab.nchunks, CHUNK, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                float(group["weight_decay"]), self._decoupled, gstep.data_ptr(),
-                None if found_inf is None else found_inf.data_ptr(), group["_ldm_scalars"].data_ptr())
-        if ext is None:
-            L.call("ldm_adam_step_dev", *args, stream_handle())
-        else:
-            L.call("ldm_adam_step_dev_ext", *args, ctypes.byref(ext), stream_handle())
+        self._launch(tab, params, group, found_inf, grad_mul, gstep.data_ptr(), group["_ldm_scalars"])
         self._tables[(gi, "dev")] = tab
         for p in params:
             torch.autograd.graph.increment_version(p)
@@ -590,8 +587,7 @@ class GradScaler:
                 continue
             _check_params(ps)
             tab = _SlotTable(ps, [p.grad for p in ps], [None] * len(ps), [None] * len(ps))
-            L.call("ldm_unscale_check", tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(),
-                   tab.nchunks, CHUNK, inv.data_ptr(), self._found_inf.data_ptr(), stream_handle())
+            L.call("ldm_unscale_check", *tab.args(), inv.data_ptr(), self._found_inf.data_ptr(), stream_handle())
             group.setdefault("_ldm_tabs", []).append(tab)   # keep alive until the launch ran
         self._unscaled.add(id(optimizer))
 

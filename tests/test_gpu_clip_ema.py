@@ -252,8 +252,12 @@ def test_fused_step_matches_float64_reference(cuda, fused_runs):
 
 
 # ---- 4. off means off -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("record", ["null", "empty"])
-def test_ext_entry_with_nothing_set_is_the_plain_step(cuda, record):
+@pytest.mark.parametrize("dev, record", [pytest.param(False, "null", id="null"), pytest.param(False, "empty", id="empty"),
+                                         pytest.param(True, "null", id="dev-null"),
+                                         pytest.param(True, "empty", id="dev-empty")])
+def test_ext_entry_with_nothing_set_is_the_plain_step(cuda, dev, record):
+    """ldm_adam_step against ldm_adam_step_ext, and (dev) the capturable pair ldm_adam_step_dev against
+    ldm_adam_step_dev_ext from a device step count of 6, with a null and with an empty record."""
     from ldm_amd import _lib as L
     from ldm_amd import optim as hoptim
     res = []
@@ -263,15 +267,20 @@ def test_ext_entry_with_nothing_set_is_the_plain_step(cuda, record):
         ms = [torch.from_numpy(a).to(cuda) for a in R.tensors(301, 1e-2)]
         vs = [torch.from_numpy(np.abs(a)).to(cuda) for a in R.tensors(302, 1e-4)]
         tab = hoptim._SlotTable(ps, gs, ms, vs)
+        step = torch.full((), 6.0, dtype=torch.float32, device=cuda)
+        scalars = torch.zeros(8, dtype=torch.float32, device=cuda)
         args = (tab.slots.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_start.data_ptr(), tab.nchunks, CHUNK,
-                1e-3, 0.9, 0.999, 1e-8, 0.01, 0, 7, None)
+                1e-3, 0.9, 0.999, 1e-8, 0.01, 0)
+        args += (step.data_ptr(), None, scalars.data_ptr()) if dev else (7, None)
+        name = "ldm_adam_step_dev" if dev else "ldm_adam_step"
         if not ext:
-            L.call("ldm_adam_step", *args, _stream())
+            L.call(name, *args, _stream())
         else:
             rec = L.AdamExt(None, None, 0.0)
-            L.call("ldm_adam_step_ext", *args, None if record == "null" else ctypes.byref(rec), _stream())
+            L.call(name + "_ext", *args, None if record == "null" else ctypes.byref(rec), _stream())
         torch.cuda.synchronize()
-        res.append((ps, ms, vs))
+        res.append((ps, ms, vs, [step]))
+    assert float(res[0][3][0]) == (7.0 if dev else 6.0)
     for a, b in zip(res[0], res[1]):
         for x, y in zip(a, b):
             assert torch.equal(x, y)
