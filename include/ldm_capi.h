@@ -582,6 +582,31 @@ int ldm_mel_gain_target(const float* C, const float* mel_out, const float* mel_c
                         const float* residual, float* mag, float* phase0, float* anchor, int32_t B, int32_t F,
                         int32_t n_mels, int32_t T, void* stream);
 
+/* ---- harmonic / percussive separation (hpss.hip) -------------------------------------------
+ * ldm_median_filter: the running median of x [B, F, T] along time (axis 1) or frequency (axis 0), win odd in 1..63,
+ * the axis continued by reflection with the edge sample repeated (d c b a | a b c d | d c b a, period 2n; scipy's
+ * mode="reflect"), so an axis shorter than the window reflects several times.  out[i] is the middle order statistic
+ * of the window, selected by rank with a position tie-break: always one of the inputs, bitwise
+ * scipy.ndimage.median_filter whatever the ties; win = 1 copies.  NaN inputs: unspecified.  out must not overlap x.
+ * B <= 65535, F <= 262140, T < 2^30.  One launch, no workspace, no atomics.  ldm_median_tile(axis): the outputs a
+ * block covers along the filtered axis (0 for a bad axis).
+ * ldm_hpss_masks: librosa's soft masks of n elements, every step a rounded fp32 operation (no contraction):
+ *   mask_h = soft(harm, margin_h perc),  mask_p = soft(perc, margin_p harm),
+ *   soft(X, R) = (X/Z)^p / ((X/Z)^p + (R/Z)^p),  Z = max(X, R);  0.5 where Z is below the smallest normal fp32.
+ * p = 1 and p = 2 multiply, any other finite p > 0 calls powf; margins >= 1; either output may be null.
+ * ldm_mask_mel_share: a bin-domain mask [B, F, T] carried to the mel grid as the energy share of what it selects,
+ *   out[b, m, t] = (sum_f M[m, f] mask[b, f, t] P[b, f, t]) / (sum_f M[m, f] P[b, f, t]),  f in [lo_m, hi_m),
+ * P [B, F, T] power, M [n_mels, F] and lohi [n_mels][2] as ldm_mel_project's; 0.5 where the denominator is below the
+ * smallest normal fp32.  Both sums add the same products in the same ascending order, so a mask in [0, 1] gives a
+ * share in [0, 1] (clamped to it), mask == 1 gives 1 and mask == 0 gives 0 exactly.  One launch. */
+int ldm_median_tile(int32_t axis);
+int ldm_median_filter(const float* x, int32_t B, int32_t F, int32_t T, int32_t axis, int32_t win, float* out,
+                      void* stream);
+int ldm_hpss_masks(const float* harm, const float* perc, int64_t n, float power, float margin_h, float margin_p,
+                   float* mask_h, float* mask_p, void* stream);
+int ldm_mask_mel_share(const float* P, const float* mask, const float* M, const int32_t* lohi, int32_t B, int32_t F,
+                       int32_t T, int32_t n_mels, float* out, void* stream);
+
 /* ---- resampling and silence trim (resample.hip) -------------------------------------------
  * The rational polyphase resampler  y[n] = sum_{j=-W..W} x[i0 + j] * taps[p][j + W],  i0 = floor(n down / up),
  * p = (n down) mod up, x zero outside [0, L); taps [up, 2W+1] fp32 on the device is the caller's filter (the

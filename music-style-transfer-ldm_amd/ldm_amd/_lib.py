@@ -149,6 +149,11 @@ SIGNATURES = {
                                      c_int32, c_vp]),
     "ldm_mel_gain_target": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_vp, c_fp, c_float, c_float, c_fp, c_fp, c_fp, c_fp,
                                       c_int32, c_int32, c_int32, c_int32, c_vp]),
+    # harmonic / percussive separation (hpss.hip)
+    "ldm_median_tile": (c_int32, [c_int32]),
+    "ldm_median_filter": (c_int32, [c_fp, c_int32, c_int32, c_int32, c_int32, c_int32, c_fp, c_vp]),
+    "ldm_hpss_masks": (c_int32, [c_fp, c_fp, c_int64, c_float, c_float, c_float, c_fp, c_fp, c_vp]),
+    "ldm_mask_mel_share": (c_int32, [c_fp, c_fp, c_fp, c_vp, c_int32, c_int32, c_int32, c_int32, c_fp, c_vp]),
     # resampling and silence trim (resample.hip)
     "ldm_resample_out_len": (c_int64, [c_int64, c_int32, c_int32]),
     "ldm_resample_f32": (c_int32, [c_fp, c_int32, c_int64, c_fp, c_int32, c_int32, c_int32, c_fp, c_vp]),

@@ -12,6 +12,9 @@ In front of the transforms (csrc/resample.hip): resample / resam
 Kaiser-windowed-sinc resampler that is this project's own definition (librosa's default, soxr_hq, cannot be
 reproduced offline), trim, librosa.effects.trim's algorithm, and chunk_mel_images, the dataset builder's batch of
 8-bit log-mel images.
+
+Harmonic / percussive separation (csrc/hpss.hip): median_filter, hpss_masks, hpss (librosa's
+decompose.hpss: medians along time and frequency, soft masks) and hpss_keep, the mel-domain keep mask of a component.
 """
 import functools
 import math
@@ -306,6 +309,81 @@ def mel_to_audio_content(mel_out, content_wave, mel_content=None, sr=SR, n_fft=N
     mag, phase0, anchor = mel_gain_target(C, mel_out, mel_content, eps, max_gain_db, anchor_db, R, sr)
     out = griffinlim(mag, n_iter, momentum, None, length, n_fft, None, phase0, phase0, anchor)
     return out[0] if one else out
+
+
+# ---- harmonic / percussive separation (csrc/hpss.hip) -----------------------------------------
+HPSS_COMPONENTS = ("percussive", "harmonic")
+
+
+def _pair(v, what):
+    """A number or a (harmonic, percussive) pair -> the pair."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"{what} must be a number or a (harmonic, percussive) pair, got {v!r}")
+        return v[0], v[1]
+    return v, v
+
+
+def check_hpss_args(kernel_size=31, power=2.0, margin=1.0, what="hpss"):
+    """ValueError for a bad kernel_size, power or margin (ops.check_median_args / check_softmask_args); returns
+    ((win_harmonic, win_percussive), (margin_harmonic, margin_percussive))."""
+    wins, margins = _pair(kernel_size, f"{what}: kernel_size"), _pair(margin, f"{what}: margin")
+    for w in wins:
+        ops.check_median_args(w, 1, what)
+    ops.check_softmask_args(power, margins[0], margins[1], what)
+    return (int(wins[0]), int(wins[1])), (float(margins[0]), float(margins[1]))
+
+
+def median_filter(S, win, axis):
+    """The running median of S [B, F, T] (or [F, T]) along frequency (axis 0) or time (axis 1) of each item: window
+    win (odd, 1..63), the ends reflected with the edge sample repeated; bitwise
+    scipy.ndimage.median_filter(mode="reflect") along that axis.  NaN inputs give an unspecified sample."""
+    ops.check_median_args(win, axis)
+    S, one = _batched(S, 3)
+    out = ops.median_filter(ops.f32c(S), win, axis)
+    return out[0] if one else out
+
+
+def hpss_masks(S, kernel_size=31, power=2.0, margin=1.0):
+    """(mask_h, mask_p) of a magnitude spectrogram S [B, F, T] (or [F, T]), librosa.decompose.hpss(mask=True): the
+    harmonic enhancement is the median along time, the percussive one the median along frequency, and
+    mask_h = softmask(harm, margin_h perc, power), mask_p = softmask(perc, margin_p harm, power), except that a bin
+    where both medians vanish gets 0.5 in both whatever the margins.  kernel_size and margin: a number or a (harmonic,
+    percussive) pair."""
+    wins, margins = check_hpss_args(kernel_size, power, margin, "hpss_masks")
+    S, one = _batched(S, 3)
+    S = ops.f32c(S)
+    harm, perc = ops.median_filter(S, wins[0], 1), ops.median_filter(S, wins[1], 0)
+    mh, mp = ops.hpss_masks(harm, perc, power, margins[0], margins[1])
+    return (mh[0], mp[0]) if one else (mh, mp)
+
+
+def hpss(y, kernel_size=31, power=2.0, margin=1.0, n_fft=N_FFT):
+    """(y_harm, y_perc) of a waveform y [B, L] (or [L]): hpss_masks of |STFT| applied to the complex STFT, each
+    component back through istft at y's length."""
+    wins, margins = check_hpss_args(kernel_size, power, margin, "hpss")
+    y, one = _batched(y, 2)
+    C, S = ops.stft(y, n_fft, None, "both_mag")
+    mh, mp = hpss_masks(S, wins, power, margins)
+    out = tuple(ops.istft(C, y.shape[-1], n_fft, None, mag=m) for m in (mh, mp))
+    return tuple(t[0] for t in out) if one else out
+
+
+def hpss_keep(y, component, kernel_size=31, power=2.0, margin=1.0, sr=SR, n_mels=128, n_fft=N_FFT):
+    """The mel-domain keep mask [n_mels, T] (T = 1 + L // hop) of the "percussive" or "harmonic" component of the
+    waveform y [L]: hpss_masks of |STFT|, carried to the mel grid as the share of each filter's energy the component
+    holds (ops.mask_mel_share on y's own power spectrogram; 0.5 where a filter sees no energy).  In [0, 1], on y's
+    device: what transfer_recording's keep= takes."""
+    if component not in HPSS_COMPONENTS:
+        raise ValueError(f"hpss_keep: component must be \"percussive\" or \"harmonic\", got {component!r}")
+    wins, margins = check_hpss_args(kernel_size, power, margin, "hpss_keep")
+    if y.dim() != 1:
+        raise ValueError(f"hpss_keep: y must be a mono waveform [L], got shape {tuple(y.shape)}")
+    y = y.unsqueeze(0)
+    M, _, _, lohi, _ = _mel_device(sr, n_fft, n_mels, y.device)
+    mh, mp = hpss_masks(ops.stft(y, n_fft, None, "mag"), wins, power, margins)
+    share = ops.mask_mel_share(ops.stft(y, n_fft, None, "power"), mp if component == "percussive" else mh, M, lohi)
+    return share[0]
 
 
 # ---- resampling, silence trim, chunk images (csrc/resample.hip; DESIGN.md §7b) -------------------------------

@@ -1127,7 +1127,8 @@ def stft_tables(n_fft, device):
 
 
 def stft(y, n_fft=2048, hop_length=None, out="complex"):
-    """y [B, L] -> [B, F, T]: complex64 (out="complex"), |S| ("mag") or |S|^2 ("power")."""
+    """y [B, L] -> [B, F, T]: complex64 (out="complex"), |S| ("mag") or |S|^2 ("power"); "both" / "both_mag": the
+    complex STFT together with |S|^2 / |S|."""
     require_device(y, dtype=None, what="stft")
     y = f32c(y)
     B, Ln = y.shape
@@ -1138,11 +1139,11 @@ def stft(y, n_fft=2048, hop_length=None, out="complex"):
         S = torch.empty((B, F, T), device=y.device, dtype=torch.complex64)
         L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), S.data_ptr(), None, 0, stream_handle())
         return S
-    if out == "both":      # (S, |S|^2) from one launch
+    if out in ("both", "both_mag"):      # (S, |S|^2) or (S, |S|) from one launch
         S = torch.empty((B, F, T), device=y.device, dtype=torch.complex64)
         P = torch.empty((B, F, T), device=y.device, dtype=torch.float32)
-        L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), S.data_ptr(), P.data_ptr(), 2,
-               stream_handle())
+        L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), S.data_ptr(), P.data_ptr(),
+               2 if out == "both" else 1, stream_handle())
         return S, P
     mag = torch.empty((B, F, T), device=y.device, dtype=torch.float32)
     L.call("ldm_stft", y.data_ptr(), B, Ln, n_fft, hop, tab.data_ptr(), None, mag.data_ptr(),
@@ -1292,6 +1293,88 @@ def mel_gain_target(C, mel_out, mel_content, Wn, mlohi, eps, max_gain, anchor_db
            mlohi.data_ptr(), eps.data_ptr(), float(max_gain), float(anchor_db), _p(residual), mag.data_ptr(),
            phase0.data_ptr(), anchor.data_ptr(), B, F, n_mels, T, stream_handle())
     return mag, phase0, anchor
+
+
+# ---- harmonic / percussive separation (hpss.hip) ---------------------------------------------
+MEDIAN_MAX_WIN = 63
+
+
+def median_tile(axis):
+    """The outputs one block of ldm_median_filter covers along the filtered axis (1: frames, 0: bins)."""
+    return int(L.load().ldm_median_tile(int(axis)))
+
+
+def check_median_args(win, axis, what="median_filter"):
+    """ValueError for a window that is not an odd integer in 1..63 or an axis other than 0 (frequency) / 1 (time)."""
+    if isinstance(win, bool) or int(win) != win or not 1 <= int(win) <= MEDIAN_MAX_WIN or int(win) % 2 == 0:
+        raise ValueError(f"{what}: win must be an odd integer in 1..{MEDIAN_MAX_WIN}, got {win!r}")
+    if axis not in (0, 1):
+        raise ValueError(f"{what}: axis must be 0 (frequency) or 1 (time) of [B, F, T], got {axis!r}")
+
+
+def check_softmask_args(power, margin_h, margin_p, what="hpss_masks"):
+    """ValueError for a power that is not finite and positive or a margin that is not finite and at least 1."""
+    if not math.isfinite(float(power)) or float(power) <= 0:
+        raise ValueError(f"{what}: power must be finite and positive, got {power}")
+    for name, m in (("harmonic", margin_h), ("percussive", margin_p)):
+        if not math.isfinite(float(m)) or float(m) < 1:
+            raise ValueError(f"{what}: the {name} margin must be finite and at least 1, got {m}")
+
+
+def median_filter(x, win, axis, out=None):
+    """The running median of x [B, F, T] fp32 along time (axis 1) or frequency (axis 0), window win (odd, 1..63),
+    reflected at the ends like scipy.ndimage.median_filter(mode="reflect") and bitwise equal to it
+    (ldm_median_filter).  out: a contiguous tensor of x's shape that shares no memory with x (None: a new one)."""
+    check_median_args(win, axis)
+    require_device(x, out, what="median_filter")
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"median_filter: x must be a non-empty [B, F, T], got {tuple(x.shape)}")
+    x = x.contiguous()
+    B, F, T = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        if tuple(out.shape) != (B, F, T) or not out.is_contiguous():
+            raise ValueError(f"median_filter: out must be a contiguous {(B, F, T)}, got {tuple(out.shape)}")
+        nbytes = x.numel() * 4
+        if out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError("median_filter: out must not alias x (the filter reads a window around every output)")
+    L.call("ldm_median_filter", x.data_ptr(), B, F, T, int(axis), int(win), out.data_ptr(), stream_handle())
+    return out
+
+
+def hpss_masks(harm, perc, power=2.0, margin_h=1.0, margin_p=1.0):
+    """(mask_h, mask_p) of ldm_hpss_masks: librosa's soft masks of the two median-filtered spectrograms, fp32 tensors
+    of one shape."""
+    check_softmask_args(power, margin_h, margin_p)
+    require_device(harm, perc, what="hpss_masks")
+    if harm.shape != perc.shape or harm.numel() == 0:
+        raise ValueError(f"hpss_masks: harm {tuple(harm.shape)} and perc {tuple(perc.shape)} must be non-empty and of "
+                         "one shape")
+    harm, perc = harm.contiguous(), perc.contiguous()
+    mask_h, mask_p = torch.empty_like(harm), torch.empty_like(perc)
+    L.call("ldm_hpss_masks", harm.data_ptr(), perc.data_ptr(), harm.numel(), float(power), float(margin_h),
+           float(margin_p), mask_h.data_ptr(), mask_p.data_ptr(), stream_handle())
+    return mask_h, mask_p
+
+
+def mask_mel_share(P, mask, M, lohi):
+    """[B, n_mels, T]: the share of each mel filter's energy that mask [B, F, T] selects from the power spectrogram
+    P [B, F, T] (ldm_mask_mel_share); M [n_mels, F] and lohi int32 [n_mels, 2] as mel_project's."""
+    require_device(P, mask, M, what="mask_mel_share")
+    require_device(lohi, dtype=torch.int32, what="mask_mel_share")
+    if P.dim() != 3 or P.numel() == 0 or mask.shape != P.shape:
+        raise ValueError(f"mask_mel_share: P and mask must be one non-empty [B, F, T], got {tuple(P.shape)} and "
+                         f"{tuple(mask.shape)}")
+    B, F, T = P.shape
+    if M.dim() != 2 or M.shape[1] != F or tuple(lohi.shape) != (M.shape[0], 2):
+        raise ValueError(f"mask_mel_share: M must be [n_mels, {F}] and lohi [n_mels, 2], got {tuple(M.shape)} and "
+                         f"{tuple(lohi.shape)}")
+    P, mask, M, lohi = P.contiguous(), mask.contiguous(), M.contiguous(), lohi.contiguous()
+    out = torch.empty((B, M.shape[0], T), device=P.device, dtype=torch.float32)
+    L.call("ldm_mask_mel_share", P.data_ptr(), mask.data_ptr(), M.data_ptr(), lohi.data_ptr(), B, F, T, M.shape[0],
+           out.data_ptr(), stream_handle())
+    return out
 
 
 # ---- whole-recording windows (longform.hip; DESIGN.md §7c) --------------------------------------------------

@@ -9,6 +9,7 @@ are crossfaded into one mel spectrogram that is vocoded once, so the phase is co
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --keep-band 0:200 --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --joint --batch 16 --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --vocoder content --out o.wav
+    python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-percussive --vocoder content --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
 """
@@ -39,7 +40,7 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                        batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None,
                        style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None, keep=None,
                        composite=True, style_map=None, joint=False, vocoder="griffinlim", max_gain_db=40.0,
-                       anchor_db=6.0, residual=True):
+                       anchor_db=6.0, residual=True, keep_component=None, hpss_kernel=31, hpss_margin=1.0):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -70,6 +71,13 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     as it is.  It is cut into windows like the content (longform.mask_windows) and every window's sampler holds the
     kept region on the content's own noising trajectory (LDM.content_style_transfer); with composite the kept region
     of every decoded window is the content window itself.  Composes with mixing and guidance.
+
+    Keeping a component (needs a solver): keep_component "percussive" or "harmonic" keeps that part of the content,
+    found by median-filter harmonic / percussive separation of its own STFT (audio.hpss_keep):
+    hpss_kernel is the median window (a number or a (harmonic, percussive) pair of odd lengths up to 63 frames / bins),
+    hpss_margin the separation margin (likewise, at least 1).  The mask is the share of each mel bin's energy the
+    component holds; with keep= as well the two are united by their element-wise maximum.  From there on it is the
+    regional transfer above, unchanged.  keep_component=None is the call it always was.
 
     Style map (needs a solver and style_refs = 1): style_map [recordings, n_mels, T_total] or [recordings, T_total]
     (non-negative, a positive sum over the recordings everywhere; longform.morph_map makes a morph from the first
@@ -121,6 +129,27 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
         if not bool(torch.isfinite(sm).all()) or bool((sm < 0).any()) or bool((sm.sum(0) <= 0).any()):
             raise ValueError("transfer_recording: style_map must be finite and non-negative, with a positive sum over "
                              "the recordings at every position")
+    if keep_component is not None:
+        if keep_component not in audio.HPSS_COMPONENTS:
+            raise ValueError(f"transfer_recording: keep_component must be \"percussive\", \"harmonic\" or None, got "
+                             f"{keep_component!r}")
+        if solver is None:
+            raise ValueError("transfer_recording: keep_component needs a solver (the reference's sampler has no "
+                             "regional keep)")
+        audio.check_hpss_args(hpss_kernel, 2.0, hpss_margin, "transfer_recording")
+        if content.dim() != 1 or content.numel() < audio.N_FFT // 2 + 1:
+            raise ValueError(f"transfer_recording: content must be a mono waveform [L] of at least "
+                             f"{audio.N_FFT // 2 + 1} samples, got shape {tuple(content.shape)}")
+        part = audio.hpss_keep(content, keep_component, kernel_size=hpss_kernel, margin=hpss_margin, sr=sr,
+                               n_mels=n_mels).cpu()
+        if keep is None:
+            keep = part
+        else:       # the union of the two, as longform.keep_mask unites its regions
+            keep = torch.as_tensor(keep, dtype=torch.float32)
+            if keep.shape != part.shape:
+                raise ValueError(f"transfer_recording: keep must be a mask [n_mels, T_total] = {list(part.shape)}, "
+                                 f"got {tuple(keep.shape)}")
+            keep = torch.maximum(keep.cpu(), part)
     if keep is not None:
         if solver is None:
             raise ValueError("transfer_recording: keep needs a solver (the reference's sampler has no regional keep)")
@@ -338,6 +367,18 @@ def parse_args(argv=None):
                         "repeatable)")
     p.add_argument("--keep-feather", type=int, default=0, dest="keep_feather", metavar="N",
                    help="ramp every kept region linearly over its N outermost frames (bins)")
+    comp = p.add_mutually_exclusive_group()
+    comp.add_argument("--keep-percussive", action="store_const", const="percussive", dest="keep_component",
+                      default=None,
+                      help="leave the percussive part of the content (its drums) as it is (needs --solver): "
+                           "median-filter harmonic / percussive separation of the content's own STFT")
+    comp.add_argument("--keep-harmonic", action="store_const", const="harmonic", dest="keep_component",
+                      help="leave the harmonic part of the content as it is and restyle its percussion (needs --solver)")
+    p.add_argument("--hpss-kernel", type=int, nargs="+", default=[31], dest="hpss_kernel", metavar="N",
+                   help="the separation's median window, odd, at most 63: one length, or the harmonic filter's frames "
+                        "and the percussive filter's bins")
+    p.add_argument("--hpss-margin", type=float, nargs="+", default=[1.0], dest="hpss_margin", metavar="M",
+                   help="the separation's margin, at least 1: one value, or harmonic and percussive")
     p.add_argument("--no-composite", action="store_false", dest="composite",
                    help="do not paste the content back over the kept region of the decoded windows")
     p.add_argument("--joint", action="store_true",
@@ -370,6 +411,17 @@ def parse_args(argv=None):
         p.error("--guidance-scale / --base-style need --solver")
     if (args.keep_time or args.keep_band) and args.solver is None:
         p.error("--keep-time / --keep-band need --solver")
+    if args.keep_component is not None and args.solver is None:
+        p.error("--keep-percussive / --keep-harmonic need --solver")
+    for flag, vals in (("--hpss-kernel", args.hpss_kernel), ("--hpss-margin", args.hpss_margin)):
+        if len(vals) > 2:
+            p.error(f"{flag} takes one or two values, got {len(vals)}")
+    args.hpss_kernel = args.hpss_kernel[0] if len(args.hpss_kernel) == 1 else tuple(args.hpss_kernel)
+    args.hpss_margin = args.hpss_margin[0] if len(args.hpss_margin) == 1 else tuple(args.hpss_margin)
+    try:
+        audio.check_hpss_args(args.hpss_kernel, 2.0, args.hpss_margin, "--hpss-kernel / --hpss-margin")
+    except ValueError as e:
+        p.error(str(e))
     if args.keep_feather < 0:
         p.error("--keep-feather must not be negative")
     if not math.isfinite(args.max_gain_db) or args.max_gain_db < 0:
@@ -405,6 +457,9 @@ def main(argv=None):
         guide["keep"] = longform.keep_mask(1 + content.numel() // HOP, 128, sr, times=args.keep_time,
                                            bands=args.keep_band, feather=args.keep_feather)
         guide["composite"] = args.composite
+    if args.keep_component is not None:   # (without the flags: today's call)
+        guide.update(keep_component=args.keep_component, hpss_kernel=args.hpss_kernel, hpss_margin=args.hpss_margin,
+                     composite=args.composite)
     if args.style_morph:
         guide["style_map"] = longform.morph_map(len(styles), 1 + content.numel() // HOP)
     if args.joint:
