@@ -607,6 +607,34 @@ int ldm_hpss_masks(const float* harm, const float* perc, int64_t n, float power,
 int ldm_mask_mel_share(const float* P, const float* mask, const float* M, const int32_t* lohi, int32_t B, int32_t F,
                        int32_t T, int32_t n_mels, float* out, void* stream);
 
+/* ---- transfer report: feature kernels of the scores (metrics.hip) ---------------------------
+ * Spectra are [B, rows, T] with T contiguous.  The fp32 entries do every step as one rounded fp32 operation in the
+ * stated order (no contraction); the float64 entries have a fixed partition that depends on the item's own length
+ * only and a fixed order, so they are bitwise repeatable and item b's result does not depend on the other items.
+ * ldm_onset_strength: db [B, n_mels, T] (a log-mel in dB), lag >= 1 -> env [B, T],
+ *   env[b, t] = (sum_m max(0, db[b, m, t] - db[b, m, t - lag])) / n_mels for t >= lag (m ascending), 0 for t < lag;
+ *   T <= lag gives all zeros.  One launch.
+ * ldm_chroma: P [B, F, T] power; bin f adds wt[f] P to pitch class cls[f] and (1 - wt[f]) P to class (cls[f] + 1) % 12,
+ *   bins ascending; cls[f] < 0: the bin contributes nothing.  chroma [B, 12, T]: each frame divided by its L2 norm
+ *   over the classes, exactly 0 where the norm is below the smallest normal fp32.  P is read once.  One launch.
+ * ldm_mfcc_moments: db [B, n_mels, T] fp32, D [n_mfcc, n_mels] float64 on the device (n_mfcc <= 32), w [B, T] fp32
+ *   frame weights or NULL (all 1) -> mom [B][1 + n_mfcc + n_mfcc (n_mfcc + 1) / 2] float64:
+ *   { sum_t w, sum_t w c_k (k ascending), sum_t w c_j c_k (j <= k, row-major) }, c_k(t) = sum_m D[k, m] db[m, t].
+ *   Float64 throughout; the coefficients are never written to memory.  workspace: ldm_mfcc_moments_workspace(B, T,
+ *   n_mfcc) doubles (0 for bad arguments).  Two launches.
+ * ldm_pair_stats: a, b [B, n] fp32, w [B, n] fp32 or NULL (all 1) -> out [B][7] float64:
+ *   { sum w, sum w a, sum w b, sum w a^2, sum w b^2, sum w a b, sum w (a - b)^2 }, operands converted to float64
+ *   first.  workspace: ldm_pair_stats_workspace(B, n) doubles.  Two launches. */
+int ldm_onset_strength(const float* db, int32_t B, int32_t n_mels, int32_t T, int32_t lag, float* env, void* stream);
+int ldm_chroma(const float* P, const int32_t* cls, const float* wt, int32_t B, int32_t F, int32_t T, float* chroma,
+               void* stream);
+int64_t ldm_mfcc_moments_workspace(int32_t B, int32_t T, int32_t n_mfcc);
+int ldm_mfcc_moments(const float* db, const double* D, const float* w, int32_t B, int32_t n_mels, int32_t T,
+                     int32_t n_mfcc, double* mom, double* workspace, void* stream);
+int64_t ldm_pair_stats_workspace(int32_t B, int64_t n);
+int ldm_pair_stats(const float* a, const float* b, const float* w, int32_t B, int64_t n, double* out, double* workspace,
+                   void* stream);
+
 /* ---- resampling and silence trim (resample.hip) -------------------------------------------
  * The rational polyphase resampler  y[n] = sum_{j=-W..W} x[i0 + j] * taps[p][j + W],  i0 = floor(n down / up),
  * p = (n down) mod up, x zero outside [0, L); taps [up, 2W+1] fp32 on the device is the caller's filter (the

@@ -154,6 +154,13 @@ SIGNATURES = {
     "ldm_median_filter": (c_int32, [c_fp, c_int32, c_int32, c_int32, c_int32, c_int32, c_fp, c_vp]),
     "ldm_hpss_masks": (c_int32, [c_fp, c_fp, c_int64, c_float, c_float, c_float, c_fp, c_fp, c_vp]),
     "ldm_mask_mel_share": (c_int32, [c_fp, c_fp, c_fp, c_vp, c_int32, c_int32, c_int32, c_int32, c_fp, c_vp]),
+    # transfer report: feature kernels of the scores (metrics.hip)
+    "ldm_onset_strength": (c_int32, [c_fp, c_int32, c_int32, c_int32, c_int32, c_fp, c_vp]),
+    "ldm_chroma": (c_int32, [c_fp, c_vp, c_fp, c_int32, c_int32, c_int32, c_fp, c_vp]),
+    "ldm_mfcc_moments_workspace": (c_int64, [c_int32, c_int32, c_int32]),
+    "ldm_mfcc_moments": (c_int32, [c_fp, c_vp, c_fp, c_int32, c_int32, c_int32, c_int32, c_vp, c_vp, c_vp]),
+    "ldm_pair_stats_workspace": (c_int64, [c_int32, c_int64]),
+    "ldm_pair_stats": (c_int32, [c_fp, c_fp, c_fp, c_int32, c_int64, c_vp, c_vp, c_vp]),
     # resampling and silence trim (resample.hip)
     "ldm_resample_out_len": (c_int64, [c_int64, c_int32, c_int32]),
     "ldm_resample_f32": (c_int32, [c_fp, c_int32, c_int64, c_fp, c_int32, c_int32, c_int32, c_fp, c_vp]),

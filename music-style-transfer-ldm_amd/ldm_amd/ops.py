@@ -1377,6 +1377,83 @@ def mask_mel_share(P, mask, M, lohi):
     return out
 
 
+# ---- transfer report: feature kernels of the scores (metrics.hip) ----------------------------
+MFCC_MAX = 32
+
+
+def _spectrum(x, what, name):
+    require_device(x, what=what)
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"{what}: {name} must be a non-empty [B, rows, T], got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def onset_strength(db, lag=1):
+    """env [B, T] of a log-mel db [B, n_mels, T] in dB (ldm_onset_strength): the mean over the mel bins of
+    max(0, db[t] - db[t - lag]); 0 for t < lag."""
+    if isinstance(lag, bool) or int(lag) != lag or int(lag) < 1:
+        raise ValueError(f"onset_strength: lag must be an integer of at least 1, got {lag!r}")
+    db = _spectrum(db, "onset_strength", "db")
+    B, n_mels, T = db.shape
+    env = torch.empty((B, T), device=db.device, dtype=torch.float32)
+    L.call("ldm_onset_strength", db.data_ptr(), B, n_mels, T, int(lag), env.data_ptr(), stream_handle())
+    return env
+
+
+def chroma(P, cls, wt):
+    """chroma [B, 12, T] of a power spectrogram P [B, F, T] (ldm_chroma): bin f gives wt[f] P to pitch class cls[f] and
+    (1 - wt[f]) P to the next; cls int32 [F] (negative: not in the band), wt fp32 [F]; frames L2-normalised."""
+    P = _spectrum(P, "chroma", "P")
+    require_device(cls, dtype=torch.int32, what="chroma")
+    require_device(wt, what="chroma")
+    B, F, T = P.shape
+    if tuple(cls.shape) != (F,) or tuple(wt.shape) != (F,):
+        raise ValueError(f"chroma: cls and wt must be [{F}], got {tuple(cls.shape)} and {tuple(wt.shape)}")
+    out = torch.empty((B, 12, T), device=P.device, dtype=torch.float32)
+    L.call("ldm_chroma", P.data_ptr(), cls.contiguous().data_ptr(), wt.contiguous().data_ptr(), B, F, T,
+           out.data_ptr(), stream_handle())
+    return out
+
+
+def mfcc_moments(db, D, weight=None):
+    """float64 [B, 1 + n + n (n + 1) / 2] on the device (ldm_mfcc_moments): per item { sum w, sum w c_k, sum w c_j c_k
+    (j <= k) } over the frames of c = D db; db [B, n_mels, T] fp32, D [n, n_mels] float64 (n <= 32), weight [B, T]
+    fp32 or None (all 1)."""
+    db = _spectrum(db, "mfcc_moments", "db")
+    require_device(D, dtype=torch.float64, what="mfcc_moments")
+    require_device(weight, what="mfcc_moments")
+    B, n_mels, T = db.shape
+    if D.dim() != 2 or D.shape[1] != n_mels or not 1 <= D.shape[0] <= MFCC_MAX:
+        raise ValueError(f"mfcc_moments: D must be [n_mfcc, {n_mels}] with 1 <= n_mfcc <= {MFCC_MAX}, got "
+                         f"{tuple(D.shape)}")
+    if weight is not None and tuple(weight.shape) != (B, T):
+        raise ValueError(f"mfcc_moments: weight must be [{B}, {T}], got {tuple(weight.shape)}")
+    n = D.shape[0]
+    weight = None if weight is None else weight.contiguous()
+    mom = torch.empty((B, 1 + n + n * (n + 1) // 2), device=db.device, dtype=torch.float64)
+    ws = torch.empty((int(L.load().ldm_mfcc_moments_workspace(B, T, n)),), device=db.device, dtype=torch.float64)
+    L.call("ldm_mfcc_moments", db.data_ptr(), D.contiguous().data_ptr(), _p(weight), B, n_mels, T, n, mom.data_ptr(),
+           ws.data_ptr(), stream_handle())
+    return mom
+
+
+def pair_stats(a, b, weight=None):
+    """float64 [B, 7] on the device (ldm_pair_stats): per item { sum w, sum w a, sum w b, sum w a^2, sum w b^2,
+    sum w a b, sum w (a - b)^2 }; a, b and weight (None: all 1) fp32 [B, n]."""
+    require_device(a, b, weight, what="pair_stats")
+    if a.dim() != 2 or a.numel() == 0 or b.shape != a.shape or (weight is not None and weight.shape != a.shape):
+        raise ValueError(f"pair_stats: a, b and weight must be one non-empty [B, n], got {tuple(a.shape)}, "
+                         f"{tuple(b.shape)}" + ("" if weight is None else f" and {tuple(weight.shape)}"))
+    a, b = a.contiguous(), b.contiguous()
+    weight = None if weight is None else weight.contiguous()
+    B, n = a.shape
+    out = torch.empty((B, 7), device=a.device, dtype=torch.float64)
+    ws = torch.empty((int(L.load().ldm_pair_stats_workspace(B, n)),), device=a.device, dtype=torch.float64)
+    L.call("ldm_pair_stats", a.data_ptr(), b.data_ptr(), _p(weight), B, n, out.data_ptr(), ws.data_ptr(),
+           stream_handle())
+    return out
+
+
 # ---- whole-recording windows (longform.hip; DESIGN.md §7c) --------------------------------------------------
 def _window_count(name, T_total, frames, overlap):
     N = int(L.load().ldm_mel_window_count(int(T_total), int(frames), int(overlap)))

@@ -10,17 +10,19 @@ are crossfaded into one mel spectrogram that is vocoded once, so the phase is co
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --joint --batch 16 --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --vocoder content --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-percussive --vocoder content --out o.wav
+    python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --report scores.json --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
 """
 import argparse
+import json
 import math
 from types import SimpleNamespace
 
 import torch
 
 from . import _pathfix  # noqa: F401
-from ldm_amd import audio, longform
+from ldm_amd import audio, longform, metrics
 
 HOP = audio.N_FFT // 4
 
@@ -40,7 +42,8 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                        batch_size=8, seed=0, n_iter=32, nnls_iters=32, max_db=80, solver=None, t_start=None,
                        style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None, keep=None,
                        composite=True, style_map=None, joint=False, vocoder="griffinlim", max_gain_db=40.0,
-                       anchor_db=6.0, residual=True, keep_component=None, hpss_kernel=31, hpss_margin=1.0):
+                       anchor_db=6.0, residual=True, keep_component=None, hpss_kernel=31, hpss_margin=1.0,
+                       report=False):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -102,7 +105,12 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     (clamped at max_gain_db), plus, with residual, the energy the style adds where the content has none; n_iter
     iterations of Griffin-Lim start from the content's phase and stay anchored to it where the gain is within
     anchor_db of unity (anchor_db <= 0: no anchor), so an untouched or composited region comes back as the content
-    itself.  `seed` plays no part in it.  Works with every solver and with solver=None."""
+    itself.  `seed` plays no part in it.  Works with every solver and with solver=None.
+
+    Report: report=True adds .report to the result, the dict of ldm_amd.metrics.transfer_report(content, audio, style)
+    (DESIGN.md §7m): onset_corr, chroma_sim, the three timbre distances and timbre_shift, and, when something was
+    kept, kept_rms_db / changed_rms_db under the mask the transfer actually used (keep=, keep_component= or their
+    union).  It is computed after the audio and changes none of it.  report=False is the call it always was."""
     n_mels = 128
     if vocoder not in ("griffinlim", "content"):
         raise ValueError(f"transfer_recording: vocoder must be \"griffinlim\" or \"content\", got {vocoder!r}")
@@ -237,6 +245,12 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
         return dict(kw, guidance_scale=float(guidance_scale),
                     base_style=xb[torch.arange(b0, b1, device=xb.device) % Nb])
 
+    def done(out):
+        res = _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N, voc)
+        if report:
+            res.report = metrics.transfer_report(content, res.audio, styles, sr=sr, keep=keep)
+        return res
+
     if guided and not isinstance(base_style, str):
         Pb = audio.melspectrogram(base_style, sr=sr, n_mels=n_mels)
         xb, _ = longform.mel_windows(Pb, frames, 0, max_db)
@@ -271,7 +285,7 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                                                               solver=solver, eta=eta, noise=noise[b0:b1],
                                                               style_weights=wb, **guide_kw(b0, b1))
                 out.append(decoded)
-        return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N, voc)
+        return done(out)
     pair = torch.arange(N, device=content.device) % Ns
     out = []
     with torch.no_grad():
@@ -286,7 +300,7 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                                                           steps=num_timesteps, solver=solver, eta=eta,
                                                           noise=noise[b0:b1], **guide_kw(b0, b1))
             out.append(decoded)
-    return _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N, voc)
+    return done(out)
 
 
 def _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N, voc=None):
@@ -396,6 +410,9 @@ def parse_args(argv=None):
                         "content's phase; 0 or less anchors nothing")
     p.add_argument("--no-residual", action="store_false", dest="residual",
                    help="--vocoder content: do not add the energy the style puts where the content is silent")
+    p.add_argument("--report", nargs="?", const="-", default=None, metavar="PATH",
+                   help="score the transfer (ldm_amd.metrics.transfer_report: rhythm and harmony kept, timbre moved "
+                        "towards the style) and print the scores as one JSON line, or write them to PATH")
     p.add_argument("--batch", type=int, default=8, help="windows per model call")
     p.add_argument("--seed", type=int, default=0)
     args = p.parse_args(argv)
@@ -467,6 +484,8 @@ def main(argv=None):
     if args.vocoder != "griffinlim":      # (without the flag: today's call)
         guide.update(vocoder=args.vocoder, max_gain_db=args.max_gain_db, anchor_db=args.anchor_db,
                      residual=args.residual)
+    if args.report is not None:           # (without the flag: today's call)
+        guide["report"] = True
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
                              num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
                              solver=args.solver, t_start=args.t_start, style_weights=args.style_weights,
@@ -474,7 +493,20 @@ def main(argv=None):
     ap.save_wav(args.out, res.audio, sr)
     print(f"{args.out}: {res.audio.numel() / sr:.1f} s, {res.N} windows of {args.frames} frames "
           f"({math.ceil(res.N / args.batch)} model calls)")
+    if args.report is not None:
+        write_report(res.report, args.report)
     return 0
+
+
+def write_report(report, path):
+    """The report as JSON: one line on standard output for "-", else the file `path` (a score without a value is NaN,
+    which json.loads reads back)."""
+    text = json.dumps(report)
+    if path == "-":
+        print(text)
+    else:
+        with open(path, "w") as f:
+            f.write(text + "\n")
 
 
 if __name__ == "__main__":
