@@ -635,6 +635,52 @@ int64_t ldm_pair_stats_workspace(int32_t B, int64_t n);
 int ldm_pair_stats(const float* a, const float* b, const float* w, int32_t B, int64_t n, double* out, double* workspace,
                    void* stream);
 
+/* ---- loudness: BS.1770 meter, true peak, look-ahead limiter (loudness.hip) -------------------
+ * Mono fp32 recordings x [B, L]; rows are independent.  No entry synchronises or allocates.
+ * ldm_loudness_hop_sums: hop_sums [B, L / hop] float64 = the sum of squares of the K-weighted signal over consecutive
+ *   hops of `hop` samples (round(0.1 sr)).  sos: 10 HOST doubles {b0, b1, b2, a1, a2} of the shelf, then of the
+ *   high-pass (a0 = 1; ldm_amd.audio.k_weighting).  Float64 throughout; the recursion is cut into chunks of
+ *   ldm_loudness_chunk(hop) samples whose true start states one small launch carries across (three launches); every
+ *   hop sum is added in sample order: bitwise repeatable and independent of B.  workspace:
+ *   ldm_loudness_workspace(B, L, hop) doubles.  L < hop writes nothing.
+ * ldm_loudness_gate: out [B, 4] float64 = {integrated LUFS, blocks passing both gates, relative threshold, blocks in
+ *   all} from hop_sums [B, n_hops]: blocks of 4 hops (400 ms, 75 % overlap), l_j = -0.691 + 10 log10(z_j) with z_j the
+ *   block's mean square, the absolute gate l_j > -70, the relative gate 10 LU under the loudness of the absolutely-gated
+ *   mean.  No block passing (n_hops < 4, silence): -inf, and a relative threshold of -inf when none passes the absolute
+ *   gate.  One block per row.
+ * ldm_loudness_gain: y = x 10^((target_lufs - stats[b][0]) / 20) with stats ldm_loudness_gate's out; a row whose
+ *   loudness is not finite gets 0 dB (y bitwise x).  gain_db [B] float64 receives the decibels applied.
+ * ldm_true_peak: out [B] = max(max |x[n]|, max |4x oversampled x|), the oversampling being ldm_resample_f32's with
+ *   taps [4, 2W+1] (up must be 4, W <= 256), fused with the maximum: the 4x signal is never written.  Bitwise
+ *   repeatable.  workspace: ldm_true_peak_workspace(B, L) floats.
+ * ldm_limit: the look-ahead true-peak limiter, one fused launch.  With c = ceiling in (0, 1] and Lh = lookahead:
+ *   p[n] = max(|x[n]|, |the four oversampling phases at n|), x = 0 outside [0, L);  r[n] = min(1, c / p[n]), 1 outside
+ *   [0, L);  m[n] = min_{|j| <= Lh} r[n + j] on [-Lh, L - 1 + Lh];  g[n] = 1 - sum_{|j| <= Lh} w_j (1 - m[n + j]), w the
+ *   2 Lh + 1 non-zero points of a Hann window normalised to sum 1;  y[n] = g[n] x[n].  g <= r in exact arithmetic; where
+ *   nothing exceeds c, g is exactly 1 and y bitwise x.  A block holds ldm_limit_tile() samples and a halo of 2 Lh + W
+ *   in LDS, so lookahead <= LDM_LIMIT_MAX_LOOKAHEAD at W = 34 (3 tile + 12 Lh + 10 W + 37 floats within 160 KiB; more is
+ *   an error).  gain [B, L] (or NULL) receives g; min_gain [B] (or NULL) its minimum per row, which needs workspace:
+ *   ldm_limit_workspace(B, L) floats.  y and gain must not alias x.
+ * ldm_peak_trim: in place, y[b] *= s_b with s_b = 1 where true_peak[b] <= ceiling and (ceiling / true_peak[b])
+ *   (1 - 2^-15) otherwise (the margin covers the rounding of a second fp32 true-peak evaluation, 2 x 70 x 2.31 x 2^-24);
+ *   trim [B] (or NULL) receives s_b. */
+#define LDM_LIMIT_MAX_LOOKAHEAD 1333
+int32_t ldm_loudness_chunk(int32_t hop);
+int64_t ldm_loudness_workspace(int32_t B, int64_t L, int32_t hop);
+int ldm_loudness_hop_sums(const float* x, int32_t B, int64_t L, int32_t hop, const double* sos, double* hop_sums,
+                          double* workspace, void* stream);
+int ldm_loudness_gate(const double* hop_sums, int32_t B, int32_t n_hops, int32_t hop, double* out, void* stream);
+int ldm_loudness_gain(const float* x, const double* stats, double target_lufs, int32_t B, int64_t L, float* y,
+                      double* gain_db, void* stream);
+int64_t ldm_true_peak_workspace(int32_t B, int64_t L);
+int ldm_true_peak(const float* x, int32_t B, int64_t L, const float* taps, int32_t up, int32_t W, float* out,
+                  float* workspace, void* stream);
+int32_t ldm_limit_tile(void);
+int64_t ldm_limit_workspace(int32_t B, int64_t L);
+int ldm_limit(const float* x, int32_t B, int64_t L, const float* taps, int32_t up, int32_t W, int32_t lookahead,
+              float ceiling, float* y, float* gain, float* min_gain, float* workspace, void* stream);
+int ldm_peak_trim(float* y, const float* true_peak, float ceiling, int32_t B, int64_t L, float* trim, void* stream);
+
 /* ---- resampling and silence trim (resample.hip) -------------------------------------------
  * The rational polyphase resampler  y[n] = sum_{j=-W..W} x[i0 + j] * taps[p][j + W],  i0 = floor(n down / up),
  * p = (n down) mod up, x zero outside [0, L); taps [up, 2W+1] fp32 on the device is the caller's filter (the

@@ -156,8 +156,20 @@ class AudioPreprocessor:
         trimmed, _ = _librosa().effects.trim(audio, top_db=top_db)
         return trimmed
 
-    def normalize_audio(self, audio):   # a TODO stub in the reference
-        pass
+    def normalize_audio(self, audio, target_lufs=-23.0, true_peak_db=-1.0):
+        """The reference's TODO stub made real: mono audio at target_sr brought to target_lufs of integrated loudness
+        (ITU-R BS.1770-4) under a look-ahead limiter that holds the true peak below true_peak_db
+        (ldm_amd.audio.loudness_normalize, on the GPU like trim_silence).  numpy in -> numpy out, CUDA tensor in -> CUDA
+        tensor out.  Silence is returned as it is.  The dataset builder does not call it: every chunk's log-mel is
+        referred to its own maximum, so a gain changes no image."""
+        from ldm_amd import audio as A
+        A.check_loudness_args(target_lufs, true_peak_db, 5.0, "normalize_audio")
+        if _is_cuda_tensor(audio):
+            y, as_np = audio, False
+        else:
+            import torch
+            y, as_np = torch.as_tensor(np.asarray(audio, dtype=np.float32)).to("cuda"), True
+        return _out(A.loudness_normalize(y, float(target_lufs), true_peak_db, sr=self.target_sr)[0], as_np)
 
     def get_mel_spectogram(self, audio, sr, n_mels=256):
         nat = _native(audio)

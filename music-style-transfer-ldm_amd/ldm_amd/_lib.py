@@ -161,6 +161,19 @@ SIGNATURES = {
     "ldm_mfcc_moments": (c_int32, [c_fp, c_vp, c_fp, c_int32, c_int32, c_int32, c_int32, c_vp, c_vp, c_vp]),
     "ldm_pair_stats_workspace": (c_int64, [c_int32, c_int64]),
     "ldm_pair_stats": (c_int32, [c_fp, c_fp, c_fp, c_int32, c_int64, c_vp, c_vp, c_vp]),
+    # loudness: BS.1770 meter, true peak, look-ahead limiter (loudness.hip)
+    "ldm_loudness_chunk": (c_int32, [c_int32]),
+    "ldm_loudness_workspace": (c_int64, [c_int32, c_int64, c_int32]),
+    "ldm_loudness_hop_sums": (c_int32, [c_fp, c_int32, c_int64, c_int32, c_vp, c_vp, c_vp, c_vp]),
+    "ldm_loudness_gate": (c_int32, [c_vp, c_int32, c_int32, c_int32, c_vp, c_vp]),
+    "ldm_loudness_gain": (c_int32, [c_fp, c_vp, ctypes.c_double, c_int32, c_int64, c_fp, c_vp, c_vp]),
+    "ldm_true_peak_workspace": (c_int64, [c_int32, c_int64]),
+    "ldm_true_peak": (c_int32, [c_fp, c_int32, c_int64, c_fp, c_int32, c_int32, c_fp, c_fp, c_vp]),
+    "ldm_limit_tile": (c_int32, []),
+    "ldm_limit_workspace": (c_int64, [c_int32, c_int64]),
+    "ldm_limit": (c_int32, [c_fp, c_int32, c_int64, c_fp, c_int32, c_int32, c_int32, c_float, c_fp, c_fp, c_fp, c_fp,
+                            c_vp]),
+    "ldm_peak_trim": (c_int32, [c_fp, c_fp, c_float, c_int32, c_int64, c_fp, c_vp]),
     # resampling and silence trim (resample.hip)
     "ldm_resample_out_len": (c_int64, [c_int64, c_int32, c_int32]),
     "ldm_resample_f32": (c_int32, [c_fp, c_int32, c_int64, c_fp, c_int32, c_int32, c_int32, c_fp, c_vp]),

@@ -15,6 +15,9 @@ reproduced offline), trim, librosa.effects.trim's algorithm, and chunk_mel_image
 
 Harmonic / percussive separation (csrc/hpss.hip): median_filter, hpss_masks, hpss (librosa's
 decompose.hpss: medians along time and frequency, soft masks) and hpss_keep, the mel-domain keep mask of a component.
+
+Loudness (csrc/loudness.hip): k_weighting, loudness_stats / integrated_loudness (ITU-R BS.1770-4),
+true_peak (4x oversampled), limit (a look-ahead true-peak limiter) and loudness_normalize, which chains them.
 """
 import functools
 import math
@@ -464,3 +467,141 @@ def chunk_mel_images(y, sr, chunk_size, n_mels=128, max_db=80):
     n = -(-y.numel() // chunk_size)
     y = torch.nn.functional.pad(ops.f32c(y), (0, n * chunk_size - y.numel())).reshape(n, chunk_size)
     return ops.mel_quantize(power_to_db(melspectrogram(y, sr=sr, n_mels=n_mels)), max_db)
+
+
+# ---- loudness: BS.1770 meter, true peak, look-ahead limiter (csrc/loudness.hip) ---------------
+LOUDNESS_INFO_KEYS = ("input_lufs", "gain_db", "output_lufs", "true_peak_db", "max_reduction_db")
+
+
+@functools.lru_cache(maxsize=None)
+def k_weighting(sr=SR):
+    """The K-weighting of ITU-R BS.1770-4 at sample rate sr: float64 [2, 5], rows {b0, b1, b2, a1, a2} (a0 = 1) of the
+    high-shelf and of the high-pass, each the bilinear transform of its analogue prototype (at 48 kHz the standard's
+    table to 1e-15).  Read-only."""
+    sr = float(sr)
+    if not math.isfinite(sr) or sr <= 0:
+        raise ValueError(f"k_weighting: the sample rate must be positive, got {sr}")
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / sr)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0,
+             2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / sr)
+    a0 = 1.0 + K / Q + K * K
+    highpass = [1.0, -2.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    out = np.array([shelf, highpass], dtype=np.float64)
+    out.setflags(write=False)
+    return out
+
+
+def loudness_hop(sr=SR):
+    """The meter's hop in samples: 100 ms, round(0.1 sr)."""
+    return int(round(0.1 * sr))
+
+
+def check_loudness_args(target_lufs=None, ceiling_db=-1.0, lookahead_ms=5.0, what="loudness_normalize"):
+    """ValueError for a non-finite target (None: not checked), a ceiling that is not finite or above 0 dB, or a
+    look-ahead that is negative or not finite."""
+    if target_lufs is not None and not math.isfinite(float(target_lufs)):
+        raise ValueError(f"{what}: the target loudness must be finite, got {target_lufs}")
+    if not math.isfinite(float(ceiling_db)) or float(ceiling_db) > 0:
+        raise ValueError(f"{what}: the true-peak ceiling must be finite and at most 0 dB, got {ceiling_db}")
+    if not math.isfinite(float(lookahead_ms)) or float(lookahead_ms) < 0:
+        raise ValueError(f"{what}: the look-ahead must be finite and not negative, got {lookahead_ms}")
+
+
+def limiter_lookahead(lookahead_ms=5.0, sr=SR):
+    """The limiter's look-ahead in samples, round(lookahead_ms sr / 1000); ValueError beyond what one tile's halo holds
+    (ops.LIMIT_MAX_LOOKAHEAD samples)."""
+    Lh = int(round(float(lookahead_ms) * sr / 1000.0))
+    if Lh > ops.LIMIT_MAX_LOOKAHEAD:
+        raise ValueError(f"limit: a look-ahead of {lookahead_ms} ms is {Lh} samples at {sr} Hz; at most "
+                         f"{ops.LIMIT_MAX_LOOKAHEAD} fit one tile's halo")
+    return Lh
+
+
+def loudness_stats(y, sr=SR):
+    """float64 [B, 4] on the device for y [B, L] (or [4] for [L]): {integrated loudness in LUFS, blocks passing both
+    gates, the relative threshold in LUFS, blocks in all} of ITU-R BS.1770-4 (mono; 400 ms blocks every 100 ms, gates at
+    -70 LUFS and 10 LU under the gated mean).  -inf when no block passes (silence, or less than 400 ms).  No host
+    synchronisation."""
+    y, one = _batched(y, 2)
+    ops.require_device(y, dtype=None, what="loudness_stats")
+    hop = loudness_hop(sr)
+    out = ops.loudness_gate(ops.loudness_hop_sums(ops.f32c(y), hop, k_weighting(sr).reshape(-1)), hop)
+    return out[0] if one else out
+
+
+def integrated_loudness(y, sr=SR):
+    """The integrated loudness in LUFS of each row of y [B, L]: float64 [B] on the device (a 0-dim tensor for [L])."""
+    return loudness_stats(y, sr)[..., 0]
+
+
+def true_peak(y, sr=SR):
+    """float32 [B] on the device: max(|y|, |y oversampled 4x|) per row of y [B, L] (a 0-dim tensor for [L]); the
+    oversampler is resample(y, sr, 4 sr)'s, fused with the maximum."""
+    y, one = _batched(y, 2)
+    ops.require_device(y, dtype=None, what="true_peak")
+    up, _, W, taps = _taps_device(sr, 4 * int(sr), y.device)
+    out = ops.true_peak(ops.f32c(y), taps, up, W)
+    return out[0] if one else out
+
+
+def _limit(y, ceiling_db, lookahead_ms, sr, want_gain=False):
+    """(out, gain, min_gain, trim) of the limiter and its trim on y [B, L] fp32 contiguous."""
+    Lh = limiter_lookahead(lookahead_ms, sr)
+    c = np.float32(10.0 ** (float(ceiling_db) / 20.0))
+    if float(c) > 10.0 ** (float(ceiling_db) / 20.0):     # the fp32 ceiling the kernels hold never exceeds the asked one
+        c = np.nextafter(c, np.float32(0.0))
+    c = float(c)
+    up, _, W, taps = _taps_device(sr, 4 * int(sr), y.device)
+    out, gain, mn = ops.limit(y, taps, up, W, Lh, c, return_gain=want_gain, return_min=True)
+    trim = ops.peak_trim_(out, ops.true_peak(out, taps, up, W), c)
+    return out, gain, mn, trim
+
+
+def limit(y, ceiling_db=-1.0, lookahead_ms=5.0, sr=SR, return_gain=False):
+    """The look-ahead true-peak limiter on y [B, L] (or [L]): the gain g = 1 - hann * (1 - min_{|j| <= Lh} r) with r =
+    min(1, c / p) and p the 4x true-peak envelope (ldm_limit), then one scalar trim per row that puts
+    the measured true peak of g y under the ceiling c = 10^(ceiling_db / 20) (g <= r only in exact arithmetic, and the
+    inter-sample peaks of g y can pass c by a hair).  A row wholly under the ceiling comes back bitwise.  No host
+    synchronisation.  return_gain: also the gain curve [B, L] (before the trim)."""
+    check_loudness_args(None, ceiling_db, lookahead_ms, "limit")
+    limiter_lookahead(lookahead_ms, sr)
+    y, one = _batched(y, 2)
+    ops.require_device(y, dtype=None, what="limit")
+    out, gain, _, _ = _limit(ops.f32c(y), ceiling_db, lookahead_ms, sr, return_gain)
+    if return_gain:
+        return (out[0], gain[0]) if one else (out, gain)
+    return out[0] if one else out
+
+
+def loudness_normalize(y, target_lufs, ceiling_db=-1.0, lookahead_ms=5.0, sr=SR):
+    """(out, info): y [B, L] (or [L]) brought to target_lufs (a number, or a float64 device tensor [B] of one target
+    per row) and limited under ceiling_db of true peak: measure, gain, limit, measure again.  info: input_lufs,
+    gain_db, output_lufs, true_peak_db, max_reduction_db (the limiter's deepest gain reduction, trim included; 0 when it
+    did not engage), each a list of B floats (a float for [L]), from one host read at the end.  A row without a finite
+    loudness (silence) gets 0 dB of gain."""
+    per_row = torch.is_tensor(target_lufs)
+    check_loudness_args(None if per_row else target_lufs, ceiling_db, lookahead_ms)
+    limiter_lookahead(lookahead_ms, sr)
+    y, one = _batched(y, 2)
+    ops.require_device(y, dtype=None, what="loudness_normalize")
+    y = ops.f32c(y)
+    stats = loudness_stats(y, sr)
+    in_lufs = stats[:, 0]
+    if per_row:     # the targets subtracted from the readings, so that one target of 0 serves every row; a target of
+        rel = stats.clone()                                     # -inf (a silent reference) leaves its row at 0 dB
+        rel[:, 0] -= target_lufs.to(stats).reshape(-1)
+        scaled, gain_db = ops.loudness_gain(y, rel, 0.0)
+    else:
+        scaled, gain_db = ops.loudness_gain(y, stats, float(target_lufs))
+    out, _, mn, trim = _limit(scaled, ceiling_db, lookahead_ms, sr)
+    tp = true_peak(out, sr)
+    table = torch.stack([in_lufs, gain_db, integrated_loudness(out, sr), 20.0 * torch.log10(tp.double()),
+                         -20.0 * torch.log10((mn * trim).double()) + 0.0]).cpu().tolist()    # the one host read
+    info = {k: (v[0] if one else v) for k, v in zip(LOUDNESS_INFO_KEYS, table)}
+    return (out[0] if one else out), info

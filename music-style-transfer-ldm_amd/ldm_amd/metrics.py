@@ -191,7 +191,8 @@ def _analyse(y, sr, n_fft, n_mels):
     return P, 10.0 * torch.log10(mel.clamp_min(AMIN)), active
 
 
-def transfer_report(content, output, style, sr=audio.SR, keep=None, n_mfcc=20, n_fft=audio.N_FFT, n_mels=128):
+def transfer_report(content, output, style, sr=audio.SR, keep=None, n_mfcc=20, n_fft=audio.N_FFT, n_mels=128,
+                    loudness=False):
     """Scores of a transfer as a dict of Python floats; content, output: mono device waveforms [L] of one length,
     style: one waveform or a list (their MFCC moments are pooled).  keep: the mask [n_mels, 1 + L // hop] in [0, 1] the
     transfer used, or None.
@@ -207,6 +208,10 @@ def transfer_report(content, output, style, sr=audio.SR, keep=None, n_mfcc=20, n
                           signal's active frames
       timbre_shift        (timbre_content_style - timbre_out_style) / timbre_content_style: 0 nothing moved, 1 arrived
       kept_rms_db, changed_rms_db   (with keep) RMS of the log-mel difference weighted by keep and by 1 - keep
+      content_lufs, output_lufs, style_lufs, output_true_peak_db
+                          (with loudness) ITU-R BS.1770-4 integrated loudness (audio.integrated_loudness; several
+                          styles: the loudness of their mean gated power) and the output's 4x true peak in dB relative
+                          to full scale; -inf for silence
 
     A score that has no value (no active frame, a constant envelope) is nan.  One host read at the end."""
     styles = list(style) if isinstance(style, (list, tuple)) else [style]
@@ -248,7 +253,13 @@ def transfer_report(content, output, style, sr=audio.SR, keep=None, n_mfcc=20, n
     for s in styles:
         _, dbs, act_s = _analyse(s, sr, n_fft, n_mels)
         moms.append(ops.mfcc_moments(torch.maximum(dbs, floor), D, act_s))
-    host = torch.cat([torch.cat(rows).reshape(-1), torch.cat(moms).reshape(-1)]).cpu().numpy()   # the one host read
+    parts = [torch.cat(rows).reshape(-1), torch.cat(moms).reshape(-1)]
+    if loudness:
+        parts.append(torch.stack([audio.integrated_loudness(y, sr) for y in [content, output] + styles]))
+        parts.append(audio.true_peak(output, sr).double().reshape(1))
+    host = torch.cat(parts).cpu().numpy()   # the one host read
+    if loudness:
+        host, loud = host[:-(3 + len(styles))], host[-(3 + len(styles)):]
 
     pairs = [PairStats(host[7 * i:7 * i + 7]) for i in range(len(rows))]
     sums = host[7 * len(rows):].reshape(len(moms), -1)
@@ -269,4 +280,9 @@ def transfer_report(content, output, style, sr=audio.SR, keep=None, n_mfcc=20, n
     }
     if keep is not None:
         rep["kept_rms_db"], rep["changed_rms_db"] = pairs[2].rms_diff, pairs[3].rms_diff
+    if loudness:
+        gated = [10.0 ** (v / 10.0) for v in loud[2:-1] if np.isfinite(v)]
+        rep["content_lufs"], rep["output_lufs"] = loud[0], loud[1]
+        rep["style_lufs"] = 10.0 * math.log10(sum(gated) / len(gated)) if gated else -math.inf
+        rep["output_true_peak_db"] = 20.0 * math.log10(loud[-1]) if loud[-1] > 0 else -math.inf
     return {k: float(v) for k, v in rep.items()}

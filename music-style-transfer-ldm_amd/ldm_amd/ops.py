@@ -1454,6 +1454,127 @@ def pair_stats(a, b, weight=None):
     return out
 
 
+# ---- loudness: BS.1770 meter, true peak, look-ahead limiter (loudness.hip) -------------------
+LIMIT_MAX_LOOKAHEAD = 1333   # ldm_capi.h LDM_LIMIT_MAX_LOOKAHEAD: samples, at the project's 4x taps (W = 34)
+
+
+def _rows(x, what):
+    require_device(x, what=what)
+    if x.dim() != 2 or x.numel() == 0:
+        raise ValueError(f"{what}: expects non-empty fp32 recordings [B, L], got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def loudness_chunk(hop):
+    """The samples one lane of ldm_loudness_hop_sums filters in sequence (the chunk of its decomposition)."""
+    return int(L.load().ldm_loudness_chunk(int(hop)))
+
+
+def limit_tile():
+    """The samples one block of ldm_limit covers."""
+    return int(L.load().ldm_limit_tile())
+
+
+def loudness_hop_sums(x, hop, sos):
+    """float64 [B, L // hop] on the device (ldm_loudness_hop_sums): the sum of squares of the K-weighted x [B, L] over
+    consecutive hops; sos: the two biquads as 10 host floats {b0, b1, b2, a1, a2} x 2."""
+    x = _rows(x, "loudness_hop_sums")
+    B, Ln = x.shape
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError(f"loudness_hop_sums: hop must be positive, got {hop}")
+    coef = (ctypes.c_double * 10)(*[float(v) for v in sos])
+    nh = Ln // hop
+    out = torch.empty((B, nh), device=x.device, dtype=torch.float64)
+    if nh == 0:
+        return out
+    ws = torch.empty((int(L.load().ldm_loudness_workspace(B, Ln, hop)),), device=x.device, dtype=torch.float64)
+    L.call("ldm_loudness_hop_sums", x.data_ptr(), B, Ln, hop, coef, out.data_ptr(), ws.data_ptr(), stream_handle())
+    return out
+
+
+def loudness_gate(hop_sums, hop):
+    """float64 [B, 4] on the device (ldm_loudness_gate): {integrated LUFS, blocks passing both gates, relative
+    threshold, blocks in all} of hop_sums [B, n_hops]."""
+    require_device(hop_sums, dtype=torch.float64, what="loudness_gate")
+    if hop_sums.dim() != 2 or hop_sums.shape[0] < 1:
+        raise ValueError(f"loudness_gate: hop_sums must be [B, n_hops], got {tuple(hop_sums.shape)}")
+    hop_sums = hop_sums.contiguous()
+    B, nh = hop_sums.shape
+    out = torch.empty((B, 4), device=hop_sums.device, dtype=torch.float64)
+    L.call("ldm_loudness_gate", hop_sums.data_ptr() if nh else None, B, nh, int(hop), out.data_ptr(), stream_handle())
+    return out
+
+
+def loudness_gain(x, stats, target_lufs):
+    """(y, gain_db): x [B, L] scaled row by row to target_lufs from stats [B, 4] (loudness_gate's); a row without a
+    finite loudness gets 0 dB.  gain_db float64 [B] on the device (ldm_loudness_gain)."""
+    x = _rows(x, "loudness_gain")
+    require_device(stats, dtype=torch.float64, what="loudness_gain")
+    B, Ln = x.shape
+    if tuple(stats.shape) != (B, 4):
+        raise ValueError(f"loudness_gain: stats must be [{B}, 4], got {tuple(stats.shape)}")
+    y = torch.empty_like(x)
+    gain_db = torch.empty((B,), device=x.device, dtype=torch.float64)
+    L.call("ldm_loudness_gain", x.data_ptr(), stats.contiguous().data_ptr(), float(target_lufs), B, Ln, y.data_ptr(),
+           gain_db.data_ptr(), stream_handle())
+    return y, gain_db
+
+
+def _taps4(taps, up, W, what):
+    require_device(taps, what=what)
+    if int(up) != 4 or tuple(taps.shape) != (4, 2 * int(W) + 1) or not taps.is_contiguous():
+        raise ValueError(f"{what}: taps must be a contiguous [4, 2W+1] table of a 4x oversampler")
+
+
+def true_peak(x, taps, up, W):
+    """float32 [B] (ldm_true_peak): max(|x|, |x oversampled 4x through taps [4, 2W+1]|) per row of x [B, L]."""
+    x = _rows(x, "true_peak")
+    _taps4(taps, up, W, "true_peak")
+    B, Ln = x.shape
+    out = torch.empty((B,), device=x.device, dtype=torch.float32)
+    ws = torch.empty((int(L.load().ldm_true_peak_workspace(B, Ln)),), device=x.device, dtype=torch.float32)
+    L.call("ldm_true_peak", x.data_ptr(), B, Ln, taps.data_ptr(), 4, int(W), out.data_ptr(), ws.data_ptr(),
+           stream_handle())
+    return out
+
+
+def limit(x, taps, up, W, lookahead, ceiling, return_gain=False, return_min=False):
+    """(y, gain or None, min_gain or None) of ldm_limit: the look-ahead true-peak limiter on x [B, L] with `lookahead`
+    samples and the linear `ceiling`; gain [B, L] and min_gain [B] only when asked for."""
+    x = _rows(x, "limit")
+    _taps4(taps, up, W, "limit")
+    lookahead = int(lookahead)
+    if not 0 <= lookahead <= LIMIT_MAX_LOOKAHEAD:
+        raise ValueError(f"limit: the look-ahead must lie in 0..{LIMIT_MAX_LOOKAHEAD} samples (one tile's halo in "
+                         f"LDS), got {lookahead}")
+    B, Ln = x.shape
+    y = torch.empty_like(x)
+    gain = torch.empty_like(x) if return_gain else None
+    mn = ws = None
+    if return_min:
+        mn = torch.empty((B,), device=x.device, dtype=torch.float32)
+        ws = torch.empty((int(L.load().ldm_limit_workspace(B, Ln)),), device=x.device, dtype=torch.float32)
+    L.call("ldm_limit", x.data_ptr(), B, Ln, taps.data_ptr(), 4, int(W), lookahead, float(ceiling), y.data_ptr(),
+           _p(gain), _p(mn), _p(ws), stream_handle())
+    return y, gain, mn
+
+
+def peak_trim_(y, tp, ceiling):
+    """In place (ldm_peak_trim): every row of y [B, L] whose true peak tp [B] exceeds `ceiling` is scaled under it;
+    returns the factors, float32 [B]."""
+    require_device(y, tp, what="peak_trim")
+    if y.dim() != 2 or y.numel() == 0 or not y.is_contiguous():
+        raise ValueError(f"peak_trim: y must be a non-empty contiguous [B, L], got {tuple(y.shape)}")
+    B, Ln = y.shape
+    if tuple(tp.shape) != (B,):
+        raise ValueError(f"peak_trim: tp must be [{B}], got {tuple(tp.shape)}")
+    s = torch.empty((B,), device=y.device, dtype=torch.float32)
+    L.call("ldm_peak_trim", y.data_ptr(), tp.contiguous().data_ptr(), float(ceiling), B, Ln, s.data_ptr(),
+           stream_handle())
+    return s
+
+
 # ---- whole-recording windows (longform.hip; DESIGN.md §7c) --------------------------------------------------
 def _window_count(name, T_total, frames, overlap):
     N = int(L.load().ldm_mel_window_count(int(T_total), int(frames), int(overlap)))

@@ -11,6 +11,7 @@ are crossfaded into one mel spectrogram that is vocoded once, so the phase is co
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-time 0:10 --vocoder content --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --keep-percussive --vocoder content --out o.wav
     python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --report scores.json --out o.wav
+    python -m models.transfer --content a.wav --style b.wav --solver dpmpp2m --loudness content --true-peak -1 --out o.wav
 
 The reference has no counterpart: its audio_reconstruction_test.py handles a single window.
 """
@@ -43,7 +44,7 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
                        style_weights=None, style_refs=1, guidance_scale=1.0, base_style=None, keep=None,
                        composite=True, style_map=None, joint=False, vocoder="griffinlim", max_gain_db=40.0,
                        anchor_db=6.0, residual=True, keep_component=None, hpss_kernel=31, hpss_margin=1.0,
-                       report=False):
+                       report=False, loudness=None, true_peak_db=-1.0):
     """content, style: mono CUDA waveforms [L] at sr.  Returns an object with audio [L], mel_power [n_mels, T_total],
     windows_out [N, 1, n_mels, frames], ref_db [N] and N.
 
@@ -110,8 +111,24 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
     Report: report=True adds .report to the result, the dict of ldm_amd.metrics.transfer_report(content, audio, style)
     (DESIGN.md §7m): onset_corr, chroma_sim, the three timbre distances and timbre_shift, and, when something was
     kept, kept_rms_db / changed_rms_db under the mask the transfer actually used (keep=, keep_component= or their
-    union).  It is computed after the audio and changes none of it.  report=False is the call it always was."""
+    union).  It is computed after the audio and changes none of it.  report=False is the call it always was.
+
+    Loudness: loudness="content" brings the output to the content's integrated loudness (ITU-R
+    BS.1770-4, audio.integrated_loudness), a float to that many LUFS, and a look-ahead limiter holds the true peak under
+    true_peak_db (audio.loudness_normalize).  It is applied after the vocoder, whichever it is; the result gains
+    .loudness, loudness_normalize's info plus content_lufs, and .report, when asked for, is computed on the normalised
+    audio.  loudness=None is the call it always was: no launch more, bitwise the same audio."""
     n_mels = 128
+    if loudness is not None:
+        if isinstance(loudness, str):
+            if loudness != "content":
+                raise ValueError(f"transfer_recording: loudness must be \"content\", a LUFS target or None, got "
+                                 f"{loudness!r}")
+        elif isinstance(loudness, bool) or not isinstance(loudness, (int, float)):
+            raise ValueError(f"transfer_recording: loudness must be \"content\", a LUFS target or None, got "
+                             f"{loudness!r}")
+        audio.check_loudness_args(None if isinstance(loudness, str) else loudness, true_peak_db, 5.0,
+                                  "transfer_recording")
     if vocoder not in ("griffinlim", "content"):
         raise ValueError(f"transfer_recording: vocoder must be \"griffinlim\" or \"content\", got {vocoder!r}")
     audio.check_vocoder_args(max_gain_db, anchor_db, "transfer_recording")
@@ -247,6 +264,11 @@ def transfer_recording(model, content, style, sr=22050, frames=512, overlap=64, 
 
     def done(out):
         res = _finish(out, ref_db, overlap, T_total, max_db, sr, n_iter, nnls_iters, seed, Ln, N, voc)
+        if loudness is not None:
+            content_lufs = audio.integrated_loudness(content, sr)
+            target = content_lufs.reshape(1) if isinstance(loudness, str) else float(loudness)
+            res.audio, res.loudness = audio.loudness_normalize(res.audio, target, true_peak_db, sr=sr)
+            res.loudness["content_lufs"] = float(content_lufs)
         if report:
             res.report = metrics.transfer_report(content, res.audio, styles, sr=sr, keep=keep)
         return res
@@ -343,6 +365,19 @@ def _span(text):
     return (a, b)
 
 
+def _loudness(text):
+    """argparse type of --loudness: "content" or a finite number of LUFS."""
+    if text == "content":
+        return text
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected \"content\" or a number of LUFS, got {text!r}") from None
+    if not math.isfinite(v):
+        raise argparse.ArgumentTypeError(f"expected a finite number of LUFS, got {text!r}")
+    return v
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="python -m models.transfer", description=__doc__.split("\n\n")[0])
     p.add_argument("--content", required=True, help="the recording to transfer (.wav, PCM16 or float32, any rate)")
@@ -413,6 +448,11 @@ def parse_args(argv=None):
     p.add_argument("--report", nargs="?", const="-", default=None, metavar="PATH",
                    help="score the transfer (ldm_amd.metrics.transfer_report: rhythm and harmony kept, timbre moved "
                         "towards the style) and print the scores as one JSON line, or write them to PATH")
+    p.add_argument("--loudness", default=None, metavar="{content|LUFS}", type=_loudness,
+                   help="bring the output to the content's integrated loudness (\"content\") or to this many LUFS "
+                        "(ITU-R BS.1770-4), under a look-ahead true-peak limiter")
+    p.add_argument("--true-peak", type=float, default=-1.0, dest="true_peak_db", metavar="DB",
+                   help="--loudness: the limiter's true-peak ceiling in dB relative to full scale, at most 0")
     p.add_argument("--batch", type=int, default=8, help="windows per model call")
     p.add_argument("--seed", type=int, default=0)
     args = p.parse_args(argv)
@@ -445,6 +485,8 @@ def parse_args(argv=None):
         p.error("--max-gain-db must be finite and non-negative")
     if not math.isfinite(args.anchor_db):
         p.error("--anchor-db must be finite")
+    if not math.isfinite(args.true_peak_db) or args.true_peak_db > 0:
+        p.error("--true-peak must be finite and at most 0 dB")
     if args.joint and args.solver is None:
         p.error("--joint needs --solver")
     if args.joint and args.overlap % 8:
@@ -486,6 +528,8 @@ def main(argv=None):
                      residual=args.residual)
     if args.report is not None:           # (without the flag: today's call)
         guide["report"] = True
+    if args.loudness is not None:         # (without the flag: today's call)
+        guide.update(loudness=args.loudness, true_peak_db=args.true_peak_db)
     res = transfer_recording(model, content, style, sr=sr, frames=args.frames, overlap=args.overlap,
                              num_timesteps=args.steps, eta=args.eta, batch_size=args.batch, seed=args.seed,
                              solver=args.solver, t_start=args.t_start, style_weights=args.style_weights,
@@ -493,6 +537,11 @@ def main(argv=None):
     ap.save_wav(args.out, res.audio, sr)
     print(f"{args.out}: {res.audio.numel() / sr:.1f} s, {res.N} windows of {args.frames} frames "
           f"({math.ceil(res.N / args.batch)} model calls)")
+    if args.loudness is not None:
+        info = res.loudness
+        print(f"loudness: content {info['content_lufs']:.2f} LUFS, output {info['input_lufs']:.2f} -> "
+              f"{info['output_lufs']:.2f} LUFS ({info['gain_db']:+.2f} dB), true peak {info['true_peak_db']:.2f} dB, "
+              f"limiter up to {info['max_reduction_db']:.2f} dB")
     if args.report is not None:
         write_report(res.report, args.report)
     return 0
