@@ -245,6 +245,16 @@ int ldm_bneck_pv(const float* u, const float* p, const float* pos_bias, float* y
 /* CA1's probabilities P [B,4,16,16] only, one block of eight waves per (sample, head): the reverse loop's form
  * (LDM_CA1P_FORM=0 keeps ldm_attention_folded_probs).  z4 token-major [B,16,512], kf [B,4,16,512], bf [B,4,16]. */
 int ldm_ca1_probs(const float* z4, const float* kf, const float* bf, float* p, int32_t B, void* stream);
+/* The keys in MFMA fragment order for ldm_ca1_probs_packed (the loop's form): kf[b][h][s][e] goes to float index
+ * (((((b*4 + h)*32 + e/16)*4 + (e%16)/4)*16 + s)*4 + e%4 of kf_packed (same size, a buffer of its own), i.e.
+ * [b][h][e chunk of 16][lg = (e%16)/4][s][4 e]: a wave's 16-byte loads of one tile of 16 keys x 16 e are one
+ * contiguous KB in lane order.  The same sums in the same order: p is bitwise ldm_ca1_probs' on the plain keys. */
+int ldm_ca1_pack_keys(const float* kf, float* kf_packed, int32_t B, void* stream);
+int ldm_ca1_probs_packed(const float* z4, const float* kf_packed, const float* bf, float* p, int32_t B, void* stream);
+/* 1 when the reverse loop keeps CA1's keys packed and runs ldm_ca1_probs_packed (the default while
+ * ldm_ca1_probs_form() is 1; LDM_BFOLD_PACKED=0 keeps the plain keys and ldm_ca1_probs, for A/B timing).  bench.py
+ * --full's kernel table times ldm_ca1_probs on plain keys. */
+int32_t ldm_bfold_packed_form(void);
 /* 1 when the reverse loop forms CA1's probabilities with ldm_ca1_probs, 0 when with ldm_attention_folded_probs
  * (LDM_CA1P_FORM=0): what bench.py times for the loop's CA1 launch. */
 int32_t ldm_ca1_probs_form(void);

@@ -28,6 +28,18 @@ namespace bf {
 constexpr int E = 512, HEADS = 4, DH = 128, S = 16, L = 16, TAPS = 9;
 constexpr int K = TAPS * HEADS * S;   // 576: k = (t * HEADS + h) * S + s
 
+// CA1's folded keys in MFMA fragment order (the packed form, ca1_probs_kernel<true>): v_mfma_f32_16x16x4_f32's lane
+// (s = lane & 15, lg = lane >> 4) holds four consecutive e of key s, so a tile of 16 keys x 16 e is stored as
+// [lg 4][s 16][4 e] and lane l's 16 bytes are the l-th of the tile's 1 KB: every quarter-wave reads two whole
+// 128-byte lines and a wave's four tiles are one contiguous 4 KB, as the step convs' packed weights are.  (The plain
+// [B][HEADS][S][E] puts the sixteen keys of a quarter-wave on sixteen different lines, 16 bytes of each; only 4 B
+// blocks run, so each CU's L1 sees all of its block's requests.)
+//   keys packed: [b][h][e chunk of 16][lg][s][4 e], a permutation within one (sample, head); same size and alignment.
+// U keeps its plain layout: the same order for U (bneck_pv_kernel, 32 B blocks) was measured no faster in the loop.
+__host__ __device__ constexpr size_t keys_packed_index(int b, int h, int s, int e) {
+    return (((((size_t)b * HEADS + h) * (E / 16) + e / 16) * 4 + (e % 16) / 4) * S + s) * 4 + e % 4;
+}
+
 // U[b][co][k] = sum_d W'[co][h*DH + d][t] * V[b][h][s][d]; kv = the style K/V projection [B][2E][S] (V rows
 // E + h*DH + d, channel-major).  Block (b, h, 32-row co tile), 288 threads = 32 co x 9 taps, V_h staged in LDS.
 __global__ __launch_bounds__(288) void bneck_fold_values_kernel(const float* __restrict__ wf, const float* __restrict__ kv,
@@ -107,7 +119,9 @@ __global__ __launch_bounds__(64 * NWV) void bneck_pv_kernel(const float* __restr
 // CA1's probabilities alone, one block of eight waves per (sample, head) (round 5) — the scores' E = 512 contraction split over the eight waves (v_mfma_f32_16x16x4_f32,
 // two 16-byte loads per lane per 16 e), the partial score tiles summed in wave order in LDS, the bias and the
 // softmax over the 16 keys by wave 0, P stored with plain stores (the next launch reads it).  The generic
-// attention kernel's PONLY instance runs the same contraction through its query / key staging.
+// attention kernel's PONLY instance runs the same contraction through its query / key staging.  PK: kf is the packed
+// keys, the wave's four chunks of it one contiguous 4 KB; the chunks, the MFMA order and the sums are the plain form's.
+template <bool PK>
 __global__ __launch_bounds__(512) void ca1_probs_kernel(const float* __restrict__ z, const float* __restrict__ kf,
                                                          const float* __restrict__ bfv, float* __restrict__ p) {
     __shared__ floatx4 red[8][64];
@@ -117,12 +131,13 @@ __global__ __launch_bounds__(512) void ca1_probs_kernel(const float* __restrict_
     const int b = blockIdx.x / HEADS, h = blockIdx.x % HEADS;
     const int e0 = wave * (E / 8);
     const float* za = z + ((size_t)b * L + col) * E + e0 + 4 * lg;
-    const float* ka = kf + (((size_t)b * HEADS + h) * S + col) * E + e0 + 4 * lg;
+    const float* ka = PK ? kf + keys_packed_index(b, h, 0, e0) + 4 * lane
+                         : kf + (((size_t)b * HEADS + h) * S + col) * E + e0 + 4 * lg;
     floatx4 zz[4], kk[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         zz[i] = *reinterpret_cast<const floatx4*>(za + 16 * i);
-        kk[i] = *reinterpret_cast<const floatx4*>(ka + 16 * i);
+        kk[i] = *reinterpret_cast<const floatx4*>(ka + (PK ? 16 * S : 16) * i);
     }
     floatx4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -151,7 +166,25 @@ __global__ __launch_bounds__(512) void ca1_probs_kernel(const float* __restrict_
     }
 }
 
+// kp = the packed order of the plain keys kf [B][HEADS][S][E]: one 16-byte piece per thread, the stores coalesced
+__global__ __launch_bounds__(256) void ca1_pack_keys_kernel(const float* __restrict__ kf, float* __restrict__ kp, int n4) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // over kp's 16-byte pieces: [b h][e chunk][lg][s]
+    if (i >= n4) return;
+    const int s = i % S, lg = i / S % 4, ch = i / (4 * S) % (E / 16), bh = i / (4 * S * (E / 16));
+    reinterpret_cast<float4*>(kp)[i] = *reinterpret_cast<const float4*>(kf + ((size_t)bh * S + s) * E + 16 * ch + 4 * lg);
+}
+
 }  // namespace bf
+
+// The loop keeps CA1's keys in the packed order for ca1_probs_kernel (LDM_BFOLD_PACKED=0: the plain layout, A/B timing;
+// the generic PONLY instance of LDM_CA1P_FORM=0 reads the plain layout, so it is plain then too).  Read once.
+bool ca1_keys_packed() {
+    static const bool on = [] {
+        const char* e = std::getenv("LDM_BFOLD_PACKED");
+        return !e || std::atoi(e) != 0;
+    }();
+    return on && ca1_probs_own();
+}
 
 // The fold applies on the canonical 2 x 8 bottleneck plane while U is no larger than W' (B <= 8);
 // LDM_BNECK_FOLD=0 keeps CA1 + the uconv bottleneck (A/B timing).
@@ -212,11 +245,21 @@ bool ca1_probs_own() {
     return on;
 }
 
-int ca1_probs(const float* z, const float* kf, const float* bfv, float* p, int B, hipStream_t st) {
+int ca1_probs(const float* z, const float* kf, const float* bfv, float* p, int B, bool packed, hipStream_t st) {
     LDM_REQUIRE(z && kf && bfv && p && B > 0, "CA1 probabilities: bad argument");
     LDM_REQUIRE((((uintptr_t)z | (uintptr_t)kf) & 15) == 0, "CA1 probabilities: operands must be 16-byte aligned");
-    hipLaunchKernelGGL(bf::ca1_probs_kernel, dim3(B * bf::HEADS), dim3(512), 0, st, z, kf, bfv, p);
+    if (packed) hipLaunchKernelGGL(bf::ca1_probs_kernel<true>, dim3(B * bf::HEADS), dim3(512), 0, st, z, kf, bfv, p);
+    else hipLaunchKernelGGL(bf::ca1_probs_kernel<false>, dim3(B * bf::HEADS), dim3(512), 0, st, z, kf, bfv, p);
     LDM_CHECK_LAUNCH("ca1_probs_kernel");
+    return 0;
+}
+
+int ca1_pack_keys(const float* kf, float* kp, int B, hipStream_t st) {
+    LDM_REQUIRE(kf && kp && kf != kp && B > 0, "CA1 pack keys: bad argument");
+    LDM_REQUIRE((((uintptr_t)kf | (uintptr_t)kp) & 15) == 0, "CA1 pack keys: operands must be 16-byte aligned");
+    const int n4 = B * bf::HEADS * bf::S * bf::E / 4;
+    hipLaunchKernelGGL(bf::ca1_pack_keys_kernel, dim3((n4 + 255) / 256), dim3(256), 0, st, kf, kp, n4);
+    LDM_CHECK_LAUNCH("ca1_pack_keys_kernel");
     return 0;
 }
 
@@ -236,7 +279,18 @@ extern "C" int ldm_bneck_pv(const float* u, const float* p, const float* pos_bia
 }
 
 extern "C" int ldm_ca1_probs(const float* z4, const float* kf, const float* bf, float* p, int32_t B, void* stream) {
-    return ldm::ca1_probs(z4, kf, bf, p, B, (hipStream_t)stream);
+    return ldm::ca1_probs(z4, kf, bf, p, B, false, (hipStream_t)stream);
 }
+
+extern "C" int ldm_ca1_pack_keys(const float* kf, float* kf_packed, int32_t B, void* stream) {
+    return ldm::ca1_pack_keys(kf, kf_packed, B, (hipStream_t)stream);
+}
+
+extern "C" int ldm_ca1_probs_packed(const float* z4, const float* kf_packed, const float* bf, float* p, int32_t B,
+                                    void* stream) {
+    return ldm::ca1_probs(z4, kf_packed, bf, p, B, true, (hipStream_t)stream);
+}
+
+extern "C" int32_t ldm_bfold_packed_form(void) { return ldm::ca1_keys_packed() ? 1 : 0; }
 
 extern "C" int32_t ldm_ca1_probs_form(void) { return ldm::ca1_probs_own() ? 1 : 0; }

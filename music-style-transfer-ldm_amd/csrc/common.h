@@ -245,6 +245,11 @@ int attention_folded_keys_map(const float* z, const float* kv, const float* kf, 
 bool bneck_fold_supported(int B, int H, int W);
 int bneck_fold_values(const float* wf, const float* kv, float* u, int B, hipStream_t st);
 int bneck_pv(const float* u, const float* p, const float* pb, float* y, int B, int dtype, hipStream_t st);
+// CA1's probabilities (packed: the keys in MFMA fragment order, the loop's form while ca1_keys_packed())
+bool ca1_probs_own();
+bool ca1_keys_packed();
+int ca1_probs(const float* z, const float* kf, const float* bfv, float* p, int B, bool packed, hipStream_t st);
+int ca1_pack_keys(const float* kf, float* kp, int B, hipStream_t st);
 
 // uconv.hip: the step kernels of the reverse loop (NHWC activations, see ldm_capi.h); the kernel and its launchers are
 // uconv_kernel.h's, shared with dec1's guided and regional-keep dispatchers (uconv_guide.hip, uconv_keep.hip)

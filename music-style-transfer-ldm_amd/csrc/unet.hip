@@ -119,9 +119,6 @@ static int64_t conv_ws_floats(const ldm_unet_weights* w) {
 }
 
 // The reverse loop's bottleneck on CA1's folded values (bfold.hip) at the canonical plane, B <= 8.
-bool ca1_probs_own();   // (bfold.hip)
-int ca1_probs(const float* z, const float* kf, const float* bfv, float* p, int B, hipStream_t st);
-
 static bool use_bneck_fold(const ldm_unet_shape& s, const ldm_unet_weights* w) {
     return w && w->use_fold && w->use_step && w->step_bneck_w && s.C == 32 && s.nf == 64 &&
            bneck_fold_supported(s.B, s.H, s.W);
@@ -471,7 +468,7 @@ static int unet_step_kernels(const ldm_unet_shape& s, const ldm_unet_weights& w,
     LDM_TRY(run(3, 3));
     if (bfold) {
         // CA1's probabilities, then the bottleneck on its folded values U (formed before the loop)
-        if (ca1_probs_own()) LDM_TRY(ca1_probs(ws.z4, ws.kf1, ws.bf1, ws.p1, s.B, st));
+        if (ca1_probs_own()) LDM_TRY(ca1_probs(ws.z4, ws.kf1, ws.bf1, ws.p1, s.B, ca1_keys_packed(), st));
         else LDM_TRY(attention_folded_probs(ws.z4, ws.kf1, ws.bf1, ws.p1, s.B, 512, 4, L1, L1, st));
         LDM_TRY(bneck_pv(ws.ubn, ws.p1, w.step_pb[1], ws.zb, s.B, w.step_dtype, st));
         return run(5, 8);
@@ -662,8 +659,13 @@ static int sample_prepare(const ldm_unet_shape* sc, const ldm_unet_weights* w, c
     if (w->use_fold) {
         LDM_TRY(attention_fold_keys_bias(ws.kv2, w->ca_wq_raw[0], w->ca_bq[0], s->B, 256, 4, S5,
                                          (float)std::sqrt(1.0 / 64.0), key_bias5, ws.kf2, ws.bf2, st));
+        // With the fold, kf1 holds CA1's keys in the packed order while ca1_keys_packed() (bfold.hip; the step's
+        // ca1_probs asks the same question): folded in the plain layout into the head of ubn (U, not yet formed, is 18
+        // times their size) and packed from there into kf1; U follows on the same stream.  The workspace keeps its size.
+        const bool kpack = lp.bfold && ca1_keys_packed();
         LDM_TRY(attention_fold_keys_bias(ws.kv1, w->ca_wq_raw[1], w->ca_bq[1], s->B, 512, 4, S6,
-                                         (float)std::sqrt(1.0 / 128.0), key_bias6, ws.kf1, ws.bf1, st));
+                                         (float)std::sqrt(1.0 / 128.0), key_bias6, kpack ? ws.ubn : ws.kf1, ws.bf1, st));
+        if (kpack) LDM_TRY(ca1_pack_keys(ws.ubn, ws.kf1, s->B, st));
         if (lp.bfold) LDM_TRY(bneck_fold_values(w->step_bneck_w, ws.kv1, ws.ubn, s->B, st));
     }
     return 0;

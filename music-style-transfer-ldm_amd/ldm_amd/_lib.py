@@ -234,6 +234,9 @@ SIGNATURES = {
     "ldm_bneck_pv": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_int32, c_int32, c_vp]),
     "ldm_ca1_probs": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_int32, c_vp]),
     "ldm_ca1_probs_form": (c_int32, []),
+    "ldm_ca1_pack_keys": (c_int32, [c_fp, c_fp, c_int32, c_vp]),
+    "ldm_ca1_probs_packed": (c_int32, [c_fp, c_fp, c_fp, c_fp, c_int32, c_vp]),
+    "ldm_bfold_packed_form": (c_int32, []),
     "ldm_set_cin1_packed": (c_int32, [c_int32]),
     "ldm_set_cin1_s1": (c_int32, [c_int32]),
     "ldm_set_flash_split": (c_int32, [c_int32]),
