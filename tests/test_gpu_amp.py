@@ -273,7 +273,8 @@ def test_conv_fwd_wgrad_lowp(cuda, name, case):
     assert rel_err(npy(dw), wr.grad.numpy()) < 1e-5
 
 
-# the double-rate 16-bit weight-gradient form (wgrad.hip wgrad_lp_kernel) at every geometry class it takes:
+# the double-rate 16-bit weight-gradient form (wgrad.hip wgrad_ring_kernel; wgrad_staged_kernel where a depth-3
+# ring does not fit the LDS: k4s2_convT_m128) at every geometry class it takes:
 # (B, Cin, H, W, Cout, k, s, p, op, transposed)
 WGRAD_LP_CASES = {
     "k3s2_vae_enc2": (2, 64, 32, 128, 128, 3, 2, 1, 0, False),     # Wq 64, BM 128, C 64

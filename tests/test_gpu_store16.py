@@ -70,7 +70,7 @@ def test_kind3_conv_store16(cuda, case, dt):
     assert torch.equal(dw16, dw32)
 
 
-# weight gradients whose splits run several chunks each, so the chunk ring (wgrad_lp16p_kernel, LDM_WGRAD_RING)
+# weight gradients whose splits run several chunks each, so the chunk ring (wgrad_ring_kernel, LDM_WGRAD_RING)
 # cycles through all its buffers and the issue cursor crosses rows and samples: every chunk geometry of the form
 # (rows of 32 positions; 16 x 2; 16 x 1; 8 x 2) and the k3 / k4, stride 1 / 2, transposed layers of the step
 RING = {   # (B, Cin, H, W, Cout, k, stride, pad, out_pad, transposed)

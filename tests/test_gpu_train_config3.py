@@ -18,7 +18,7 @@ the autocast output semantics to 1.5 e + 1e-4 of the bf16 reference and 2 e + 1e
 
 test_config3_every_conv_instance re-runs every conv forward / data-gradient / weight-gradient call of one
 bf16 step at its B=32 geometry (whatever kernel instance the plan picks: tconv_kernel, conv_mfma_kernel,
-wgrad_lp_kernel, the Cin = 1 and Cout = 1 kernels ...) on random operands against float64 of the operands
+wgrad_ring_kernel, the Cin = 1 and Cout = 1 kernels ...) on random operands against float64 of the operands
 (rounded to bf16 where the instance rounds; 1e-5).
 """
 import math

@@ -1,11 +1,14 @@
-"""The fp32-map weight gradient on its LDS-DMA chunk ring (csrc/wgrad.hip wgrad_lpp_kernel, round 6): the train
-step's UNet-level layers (maps below the 16-bit storage threshold stay fp32; reference layers model.py:178-194,
-their gradients under train.py:174's autocast) at bf16 / fp16 operand precision.
+"""The fp32-map weight gradient on its LDS-DMA chunk ring (csrc/wgrad.hip wgrad_ring_kernel, 4-byte elements): the
+train step's UNet-level layers (maps below the 16-bit storage threshold stay fp32; reference layers
+model.py:178-194, their gradients under train.py:174's autocast) at bf16 / fp16 operand precision.
 
 * against float64 of the identically rounded operands (the weight gradient of a conv is the correlation of the
   input with the output gradient): max |dw - dw64| <= 1e-5 max |dw64|;
-* bitwise against the double-buffered form it replaces (wgrad_lp_kernel, LDM_WGRAD_RING=2, run in a child
-  process): same blocks, chunks, k-steps and MFMA order, so the same bits."""
+* bitwise against the register-staged form (wgrad_staged_kernel, LDM_WGRAD_RING=2, run in a child process), which
+  synchronises with plain __syncthreads and none of the ring's counted waits: same blocks, chunks, k-steps and
+  MFMA order, so the same bits.  On fp32 maps (the UNet layers) and on bf16 maps (the ring of 2-byte elements
+  against the staged form's 16-bit widening path, three small geometries that still cycle the ring and cross rows
+  and samples)."""
 import os
 import subprocess
 import sys
@@ -68,14 +71,35 @@ def test_wgrad_fp32_maps_ring_vs_float64(cuda, case, dt):
     assert err <= 1e-5, err
 
 
+CASES16 = ("k3s1_rows8x2", "k3s1_rows16x1", "k3s2_rows16x2")   # of test_gpu_store16.RING, on bf16 maps
+
+
+def _dw16(case, dev):
+    """dW from bf16-stored maps (values rounded to bf16 first, as test_gpu_store16._q does)."""
+    import test_gpu_store16 as s16
+    from ldm_amd import ops
+    B, Cin, H, W, Cout, k, s, p, op, tr = s16.RING[case]
+    desc = ops.make_desc(B, Cin, H, W, Cout, k, k, s, p, op, tr)
+    x16 = s16._q(_rand((B, Cin, H, W), 21), 2)[0]
+    g16 = s16._q(_rand((B, Cout, desc.Hout, desc.Wout), 22), 2)[0]
+    assert ops.wgrad_storage16(desc, 2), case
+    dw = ops.conv_backward_weight(x16.to(dev), g16.to(dev), desc, dtype=2)
+    torch.cuda.synchronize()
+    return dw
+
+
 def test_wgrad_fp32_maps_ring_bitwise_double_buffered(cuda, tmp_path):
     out = tmp_path / "db.pt"
     code = ("import sys, torch; sys.path[:0] = [%r, %r, %r]; import test_gpu_wgrad_ring32 as m; "
-            "torch.save({c: m._dw(c, 2, torch.device('cuda:0'))[2].cpu() for c in sorted(m.CASES)}, %r)"
+            "d = torch.device('cuda:0'); r = {c: m._dw(c, 2, d)[2].cpu() for c in sorted(m.CASES)}; "
+            "r.update({c: m._dw16(c, d).cpu() for c in m.CASES16}); torch.save(r, %r)"
             % (ROOT, os.path.join(ROOT, "music-style-transfer-ldm_amd"), os.path.join(ROOT, "tests"), str(out)))
     env = dict(os.environ, LDM_WGRAD_RING="2")
     subprocess.run([sys.executable, "-c", code], env=env, check=True, timeout=240)
     db = torch.load(str(out), weights_only=True)
     for c in sorted(CASES):
         dw = _dw(c, 2, cuda)[2].cpu()
+        assert torch.equal(dw, db[c]), (c, float((dw - db[c]).abs().max()))
+    for c in CASES16:   # the 2-byte ring against the staged form widening the same bf16 maps
+        dw = _dw16(c, cuda).cpu()
         assert torch.equal(dw, db[c]), (c, float((dw - db[c]).abs().max()))

@@ -1,5 +1,6 @@
 """Time the 16-bit weight gradient of the train step's large-plane layers (B = 32, 1x128x512 mels):
-the double-rate form (wgrad_lp_kernel) against the tap-shared form (LDM_WGRAD_LP=0).
+the double-rate form (wgrad_ring_kernel; wgrad_staged_kernel with LDM_WGRAD_RING=2) against the tap-shared form
+(LDM_WGRAD_LP=0).
 python tools/time_wgrad.py [bf16|fp16]"""
 import os
 import sys
